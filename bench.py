@@ -2,6 +2,7 @@
 """Benchmark of the kfec hot path: device-resident Reed-Solomon encode + decode on MI355X.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config 20:3|10:3dec|200:55|20:3loss1]
+                    [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 bench.py --gpus N ...
 
 Both forms run one process per GPU: without a launcher's WORLD_SIZE, `--gpus N > 1` spawns the N rank
@@ -15,7 +16,14 @@ time, in GiB/s.  Shard groups are independent, so each rank owns a contiguous ra
 space (kcptube_amd.partition.group_range; weak scaling, no collective on the data path; gloo carries only
 the timing barrier, the max-reduce and the verification flag).
 
-Also reported (rank 0):
+A plain run sets up, warms up, times the K steps and prints the line with value and ms_per_step (and the
+event-timed encode_ms / decode_ms of the same steps).  --dump-outputs DIR then writes what the last timed step
+left to its caller -- parity, recovered shards, their data-shard ids and the per-group status, of a sample of
+groups fixed by the arguments -- as DIR/<name>.npy; inputs are generated from a fixed seed, so two builds run
+with the same arguments can be compared output for output.
+
+With --full, after the timed steps, the recovered shards are verified bit-exact on the device
+(verified_bit_exact; exit 3 if not) and rank 0 also reports:
   roofline      the dominant kernel (the encode MAC launch; decode for decode-only configs) from HIP events
                 on its stream, plus the whole step (encode + decode algorithmic bytes / ms_per_step) as total
                 and read-only fractions of the 8 TB/s spec AND of this box's measured linear-read ceiling
@@ -71,13 +79,58 @@ def parse():
     p.add_argument("--pitch", type=int, default=0,
                    help="bytes per shard slot in HBM (default: kcp_mtu, rows back to back; a larger pitch only "
                         "aligns the rows -- same shard bytes, same algorithmic traffic -- and is never the headline)")
-    p.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline leg")
+    p.add_argument("--full", action="store_true",
+                   help="after the timed steps also verify the recovered shards bit-exact (exit 3 if not), measure "
+                        "the same-run ceilings of the roofline and run the CPU baseline; a plain run sets up, warms "
+                        "up, times the steps and prints the headline line only")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps write what the last step computed (parity, recovered shards, their "
+                        "ids, status) of a fixed seeded sample of groups as DIR/<name>.npy (float32; group ids float64)")
+    p.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU baseline leg")
     p.add_argument("--cpu-seconds", type=float, default=16.0, help="target CPU-seconds of the baseline sample")
     p.add_argument("--cpu-groups", type=int, default=1 << 16, help="distinct groups of the CPU baseline sample")
     p.add_argument("--rehearsal", action="store_true",
                    help="allow more ranks than visible GPUs (ranks share devices as LOCAL_RANK %% count; also "
                         "KFEC_BENCH_REHEARSAL=1): a test of the partition, never a scaling number")
-    return p.parse_args()
+    args = p.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        p.error("--steps must be at least 1 and --warmup at least 0")
+    return args
+
+
+DUMP_BUDGET = 48 << 20  # bytes of .npy that --dump-outputs may write over all ranks (float32 per output byte)
+
+
+def dump_groups(G: int, R: int, B: int, world: int = 1):
+    """The local groups --dump-outputs writes: all of them where they fit this rank's share of DUMP_BUDGET, else a
+    sample that depends only on SEED and the shapes (sorted), so two builds run with the same arguments dump the
+    same groups."""
+    import numpy as np
+    n = max(1, min(G, DUMP_BUDGET // world // (4 * (2 * R * B + R + 1) + 8)))
+    if n == G:
+        return np.arange(G, dtype=np.int64)
+    return np.sort(np.random.default_rng(SEED).choice(G, size=n, replace=False)).astype(np.int64)
+
+
+def dump_outputs(torch, path, world, rank, g0, B, do_enc, par, out, idx, st):
+    """Write the arrays the last timed step left to its caller for the groups of dump_groups(): parity (encode
+    configs), recovered shards with their data-shard ids (rows past a group's erasure count are unspecified in
+    `out` and written as 0) and the per-group status."""
+    import numpy as np
+    G, R, _ = out.shape
+    sel = dump_groups(G, R, B, world)
+    suffix = f".rank{rank}" if world > 1 else ""
+    os.makedirs(path, exist_ok=True)
+    t = torch.from_numpy(sel).to(out.device)
+    ix = idx[t].cpu().numpy()
+    rec = out[t][..., :B].cpu().numpy()
+    rec[ix == 0xFF] = 0
+    arrays = {"groups": (sel + g0).astype(np.float64), "recovered": rec.astype(np.float32),
+              "recovered_ids": ix.astype(np.float32), "status": st[t].cpu().numpy().astype(np.float32)}
+    if do_enc:
+        arrays["parity"] = par[t][..., :B].cpu().numpy().astype(np.float32)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, f"{name}{suffix}.npy"), a)
 
 
 def rehearsal_allowed(args) -> bool:
@@ -402,6 +455,107 @@ def spawn_ranks(cmd: list[str], n: int, poll_s: float = 0.2) -> int:
     return rc
 
 
+def measure_roofline(torch, args, dev, K, N, B, G, pitch, do_enc, n_rec, n_dec, enc_ms, dec_ms, ms_per_step,
+                     data, par, masks, out, idx, st) -> dict:
+    """--full: this rank's `roofline` record.  The algorithmic bytes of the timed launches over their measured
+    durations, against ceilings measured now, in runs of their own on the bench's tensors (which they overwrite)."""
+    R = N - K
+    # roofline: algorithmic HBM bytes per launch (SURVEY 8(d)) / measured launch duration (this rank's share)
+    enc_bytes = G * (K + R) * B                    # read K*B, write R*B per group
+    dec_bytes = n_dec * K * B + n_rec * B          # read the K selected shares, write the m recovered
+    enc_read = G * K * B
+    dec_read = n_dec * K * B
+    if do_enc:
+        dom_bytes, dom_read, dom_ms = enc_bytes, enc_read, enc_ms
+        dom_name = "mac_kernel<32,MT,encode> (kfec_encode_batch)"
+    else:
+        dom_bytes, dom_read, dom_ms = dec_bytes, dec_read, dec_ms
+        dom_name = "decode_prep + syn_kernel (kfec_decode_batch)"
+    achieved = dom_bytes / (dom_ms * 1e-3) / 1e9
+    achieved_read = dom_read / (dom_ms * 1e-3) / 1e9
+    step_bytes = (enc_bytes if do_enc else 0) + dec_bytes
+    step_read = (enc_read if do_enc else 0) + dec_read
+    step_ms_local = ms_per_step  # whole step, wall clock, all launches and gaps included
+    step_gbs = step_bytes / (step_ms_local * 1e-3) / 1e9
+    step_read_gbs = step_read / (step_ms_local * 1e-3) / 1e9
+
+    traffic = None
+    pmc = os.path.join(ROOT, "profiles", "pmc_traffic.json")
+    if os.path.exists(pmc):
+        try:
+            with open(pmc) as f:
+                tr = json.load(f).get(args.config if pitch == B else f"{args.config}@p{pitch}")
+            if tr and tr.get("groups") == G and tr.get("pitch", B) == pitch:
+                traffic = tr.get("hbm_bytes_per_launch")
+        except (OSError, ValueError):
+            traffic = None
+
+    # ceilings, measured on EVERY rank's own GPU after the timed region and the verification (the buffers they
+    # write -- out, idx, st -- have been checked already): the linear-read ceiling, the ideal streaming form of the
+    # dominant launch's byte mix (calib_mix), and the product's own kernels with the GF arithmetic removed
+    # (tools/libkfec_arithfree.so: same grid, loads and stores); the mix ceiling is the faster of the two
+    calib = Calib()
+    read_ceiling = calib.read_ceiling(torch, data)
+    if do_enc:
+        mix_r, mix_w, mix_g = K * B, R * B, G
+    else:
+        mix_r, mix_w, mix_g = K * B, (n_rec * B / n_dec if n_dec else 0), max(n_dec, 1)
+    mix_calib = calib.mix_ceiling(torch, data, out, mix_g, mix_r, mix_w) if args.config != "200:55" else None
+    af = ArithFree(K, N)
+    if do_enc:
+        af_ms = af.encode_ms(torch, data, out, B)
+    else:
+        af_ms = af.decode_ms(torch, data, par, masks, out, idx, st, B, dev)
+    af.close()
+    af_rate = dom_bytes / (af_ms * 1e-3) / 1e9 if af_ms else None
+    mix_ceiling = max(mix_calib or 0.0, af_rate or 0.0) or None
+    roof = {"bound": "hbm", "kernel": dom_name, "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS,
+            "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic,
+            "algorithmic_bytes_per_launch": dom_bytes, "avg_launch_ms": round(dom_ms, 4),
+            "achieved_read": round(achieved_read, 1), "frac_read": round(achieved_read / HBM_PEAK_GBS, 4),
+            # the whole step (encode + decode) against the spec peak and the measured read ceiling
+            "step_bytes": step_bytes, "step_read_bytes": step_read, "step_ms": round(step_ms_local, 4),
+            "step_achieved": round(step_gbs, 1), "step_frac": round(step_gbs / HBM_PEAK_GBS, 4),
+            "step_frac_read": round(step_read_gbs / HBM_PEAK_GBS, 4),
+            "read_ceiling": round(read_ceiling, 1) if read_ceiling else None,
+            "step_frac_of_ceiling": round(step_gbs / read_ceiling, 4) if read_ceiling else None,
+            "step_frac_read_of_ceiling": round(step_read_gbs / read_ceiling, 4) if read_ceiling else None,
+            "frac_of_ceiling": round(achieved / read_ceiling, 4) if read_ceiling else None,
+            # the same launch against the faster of two ideal forms of its own read + write mix, both timed in this
+            # run: calib_mix (one workgroup per group, contiguous, no arithmetic) and the arithmetic-free build of the
+            # product kernel itself (best of 5 launches; the product's time is the mean over the timed steps)
+            "mix_ceiling": round(mix_ceiling, 1) if mix_ceiling else None,
+            "mix_ceiling_kind": (None if not mix_ceiling else
+                                 "arithfree" if (af_rate or 0) >= (mix_calib or 0) else "calib_mix"),
+            "mix_ceiling_calib": round(mix_calib, 1) if mix_calib else None,
+            "arithfree_ms": round(af_ms, 4) if af_ms else None,
+            "arithfree_ms_by_occupancy": af.last, "mix_calib_GBps_by_occupancy": calib.mix_last,
+            "arithfree_GBps": round(af_rate, 1) if af_rate else None,
+            "mix_ceiling_bytes_per_group": [mix_r, round(mix_w, 1)],
+            "frac_of_mix_ceiling": round(achieved / mix_ceiling, 4) if mix_ceiling else None}
+    if args.config == "200:55":
+        # VALU-bound: byte-MACs per second of each kernel against the perm MAC's issue bound on this box
+        cus = torch.cuda.get_device_properties(dev).multi_processor_count
+        ceil_mac = calib.gfmac_ceiling(torch, dev, cus)
+        enc_mac = G * R * K * B / (enc_ms * 1e-3)
+        dec_mac = n_rec * K * B / (dec_ms * 1e-3)
+        roof.update({"bound": "valu", "unit": "byte-MAC/s", "achieved": round(enc_mac, 0),
+                     "peak": round(ceil_mac, 0) if ceil_mac else None,
+                     "frac": round(enc_mac / ceil_mac, 4) if ceil_mac else None,
+                     "decode_achieved": round(dec_mac, 0),
+                     "decode_frac": round(dec_mac / ceil_mac, 4) if ceil_mac else None,
+                     "hbm_achieved": round(achieved, 1), "hbm_frac": round(achieved / HBM_PEAK_GBS, 4),
+                     "ceiling_kernel": "issue bound of the paired perm MAC: 8 byte-MACs per lane per (6 v_perm_b32 + "
+                                       "3 v_bitop3_b32) at the rates tools/calib.hip measures on this box",
+                     "issue_bound_single": round(calib.mac_last["single"], 0) if calib.mac_last else None,
+                     "frac_of_single_bound": (round(enc_mac / calib.mac_last["single"], 4)
+                                              if calib.mac_last else None)})
+
+    roof["decode_hbm_GBps"] = round(dec_bytes / (dec_ms * 1e-3) / 1e9, 1)
+    roof["roundtrip_hbm_GBps"] = round(step_bytes / ((enc_ms if do_enc else 0) + dec_ms) / 1e6, 1)
+    return roof
+
+
 def main():
     args = parse()
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
@@ -505,15 +659,25 @@ def main():
     enc_ms = sum(ev[i][0].elapsed_time(ev[i][1]) for i in range(n_ev)) / n_ev
     dec_ms = sum(ev[i][1].elapsed_time(ev[i][2]) for i in range(n_ev)) / n_ev
 
-    # correctness of what was timed (untimed): every erased data shard recovered bit-exact
-    mism = torch.zeros(1, dtype=torch.int64, device=dev)
-    c.verify_recovered(data, out, idx, mism, B=B)
-    torch.cuda.synchronize()
-    n_rec = int((idx != 0xFF).sum().item())
-    n_dec = int((idx[:, 0] != 0xFF).sum().item()) if R > 0 else 0  # groups with m > 0 (m = 0 reads nothing)
-    # (i.i.d. loss: a group that lost more than R shards has too few shares, status 1, as the reference's {})
-    st_ok = int(st.max().item()) <= (1 if mode == 2 else 0)
-    ok = int(mism.item()) == 0 and st_ok and n_rec > 0
+    payload = K * B * total_groups * args.steps
+    value = payload / elapsed / 2**30
+    ms_per_step = elapsed / args.steps * 1e3
+
+    # what the last timed step computed, before anything below writes to the same buffers
+    if args.dump_outputs:
+        dump_outputs(torch, args.dump_outputs, world, rank, g0, B, do_enc, par, out, idx, st)
+
+    # --full: correctness of what was timed (untimed): every erased data shard recovered bit-exact
+    ok, n_rec, n_dec = True, 0, 0
+    if args.full:
+        mism = torch.zeros(1, dtype=torch.int64, device=dev)
+        c.verify_recovered(data, out, idx, mism, B=B)
+        torch.cuda.synchronize()
+        n_rec = int((idx != 0xFF).sum().item())
+        n_dec = int((idx[:, 0] != 0xFF).sum().item()) if R > 0 else 0  # groups with m > 0 (m = 0 reads nothing)
+        # (i.i.d. loss: a group that lost more than R shards has too few shares, status 1, as the reference's {})
+        st_ok = int(st.max().item()) <= (1 if mode == 2 else 0)
+        ok = int(mism.item()) == 0 and st_ok and n_rec > 0
     # KFEC_BENCH_DIGEST=P (tests): the global group space cut into P parts (group_range), one SHA-256 per part
     # over its parity, recovered bytes and recovered ids, gathered in part order and combined (a checksum of
     # checksums): equal for every world size that divides P iff no group was lost, duplicated or changed
@@ -541,108 +705,18 @@ def main():
     ok = int(counts[0].item()) == 0
     n_rec_all, n_dec_all = int(counts[1].item()), int(counts[2].item())
 
-    payload = K * B * total_groups * args.steps
-    value = payload / elapsed / 2**30
-    ms_per_step = elapsed / args.steps * 1e3
-
-    # roofline: algorithmic HBM bytes per launch / measured launch duration (this rank's share)
-    enc_bytes = G * (K + R) * B                    # read K*B, write R*B per group
-    dec_bytes = n_dec * K * B + n_rec * B          # read the K selected shares, write the m recovered
-    enc_read = G * K * B
-    dec_read = n_dec * K * B
-    if do_enc:
-        dom_bytes, dom_read, dom_ms = enc_bytes, enc_read, enc_ms
-        dom_name = "mac_kernel<32,MT,encode> (kfec_encode_batch)"
-    else:
-        dom_bytes, dom_read, dom_ms = dec_bytes, dec_read, dec_ms
-        dom_name = "decode_prep + syn_kernel (kfec_decode_batch)"
-    achieved = dom_bytes / (dom_ms * 1e-3) / 1e9
-    achieved_read = dom_read / (dom_ms * 1e-3) / 1e9
-    step_bytes = (enc_bytes if do_enc else 0) + dec_bytes
-    step_read = (enc_read if do_enc else 0) + dec_read
-    step_ms_local = ms_per_step  # whole step, wall clock, all launches and gaps included
-    step_gbs = step_bytes / (step_ms_local * 1e-3) / 1e9
-    step_read_gbs = step_read / (step_ms_local * 1e-3) / 1e9
-
-    traffic = None
-    pmc = os.path.join(ROOT, "profiles", "pmc_traffic.json")
-    if os.path.exists(pmc):
-        try:
-            with open(pmc) as f:
-                tr = json.load(f).get(args.config if pitch == B else f"{args.config}@p{pitch}")
-            if tr and tr.get("groups") == G and tr.get("pitch", B) == pitch:
-                traffic = tr.get("hbm_bytes_per_launch")
-        except (OSError, ValueError):
-            traffic = None
-
-    # ceilings, measured on EVERY rank's own GPU after the timed region and the verification (the buffers they
-    # write -- out, idx, st -- have been checked already): the linear-read ceiling, the ideal streaming form of the
-    # dominant launch's byte mix (calib_mix), and the product's own kernels with the GF arithmetic removed
-    # (tools/libkfec_arithfree.so: same grid, loads and stores); the mix ceiling is the faster of the two
-    calib = Calib()
-    read_ceiling = calib.read_ceiling(torch, data)
-    if do_enc:
-        mix_r, mix_w, mix_g = K * B, R * B, G
-    else:
-        mix_r, mix_w, mix_g = K * B, (n_rec * B / n_dec if n_dec else 0), max(n_dec, 1)
-    mix_calib = calib.mix_ceiling(torch, data, out, mix_g, mix_r, mix_w) if args.config != "200:55" else None
-    af = ArithFree(K, N)
-    if do_enc:
-        af_ms = af.encode_ms(torch, data, out, B)
-    else:
-        af_ms = af.decode_ms(torch, data, par, masks, out, idx, st, B, dev)
-    af.close()
-    af_rate = dom_bytes / (af_ms * 1e-3) / 1e9 if af_ms else None
-    mix_ceiling = max(mix_calib or 0.0, af_rate or 0.0) or None
-    roof = {"bound": "hbm", "kernel": dom_name, "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS,
-            "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic,
-            "algorithmic_bytes_per_launch": dom_bytes, "avg_launch_ms": round(dom_ms, 4),
-            "achieved_read": round(achieved_read, 1), "frac_read": round(achieved_read / HBM_PEAK_GBS, 4),
-            # the whole step (encode + decode) against the spec peak and the measured read ceiling
-            "step_bytes": step_bytes, "step_read_bytes": step_read, "step_ms": round(step_ms_local, 4),
-            "step_achieved": round(step_gbs, 1), "step_frac": round(step_gbs / HBM_PEAK_GBS, 4),
-            "step_frac_read": round(step_read_gbs / HBM_PEAK_GBS, 4),
-            "read_ceiling": round(read_ceiling, 1) if read_ceiling else None,
-            "step_frac_of_ceiling": round(step_gbs / read_ceiling, 4) if read_ceiling else None,
-            "step_frac_read_of_ceiling": round(step_read_gbs / read_ceiling, 4) if read_ceiling else None,
-            "frac_of_ceiling": round(achieved / read_ceiling, 4) if read_ceiling else None,
-            # the same launch against the faster of two ideal forms of its own read + write mix, both timed in this
-            # run: calib_mix (one workgroup per group, contiguous, no arithmetic) and the arithmetic-free build of the
-            # product kernel itself (best of 5 launches; the product's time is the mean over the timed steps)
-            "mix_ceiling": round(mix_ceiling, 1) if mix_ceiling else None,
-            "mix_ceiling_kind": (None if not mix_ceiling else
-                                 "arithfree" if (af_rate or 0) >= (mix_calib or 0) else "calib_mix"),
-            "mix_ceiling_calib": round(mix_calib, 1) if mix_calib else None,
-            "arithfree_ms": round(af_ms, 4) if af_ms else None,
-            "arithfree_ms_by_occupancy": af.last, "mix_calib_GBps_by_occupancy": calib.mix_last,
-            "arithfree_GBps": round(af_rate, 1) if af_rate else None,
-            "mix_ceiling_bytes_per_group": [mix_r, round(mix_w, 1)],
-            "frac_of_mix_ceiling": round(achieved / mix_ceiling, 4) if mix_ceiling else None}
-    if args.config == "200:55":
-        # VALU-bound: byte-MACs per second of each kernel against the perm MAC's issue bound on this box
-        cus = torch.cuda.get_device_properties(dev).multi_processor_count
-        ceil_mac = calib.gfmac_ceiling(torch, dev, cus)
-        enc_mac = G * R * K * B / (enc_ms * 1e-3)
-        dec_mac = n_rec * K * B / (dec_ms * 1e-3)
-        roof.update({"bound": "valu", "unit": "byte-MAC/s", "achieved": round(enc_mac, 0),
-                     "peak": round(ceil_mac, 0) if ceil_mac else None,
-                     "frac": round(enc_mac / ceil_mac, 4) if ceil_mac else None,
-                     "decode_achieved": round(dec_mac, 0),
-                     "decode_frac": round(dec_mac / ceil_mac, 4) if ceil_mac else None,
-                     "hbm_achieved": round(achieved, 1), "hbm_frac": round(achieved / HBM_PEAK_GBS, 4),
-                     "ceiling_kernel": "issue bound of the paired perm MAC: 8 byte-MACs per lane per (6 v_perm_b32 + "
-                                       "3 v_bitop3_b32) at the rates tools/calib.hip measures on this box",
-                     "issue_bound_single": round(calib.mac_last["single"], 0) if calib.mac_last else None,
-                     "frac_of_single_bound": (round(enc_mac / calib.mac_last["single"], 4)
-                                              if calib.mac_last else None)})
-
-    # every rank's own timing, device and fractions, gathered after the timed region (per_rank in the JSON line)
+    roof, decode_hbm, roundtrip_hbm = None, None, None
+    if args.full:
+        roof = measure_roofline(torch, args, dev, K, N, B, G, pitch, do_enc, n_rec, n_dec, enc_ms, dec_ms, ms_per_step,
+                                data, par, masks, out, idx, st)
+        decode_hbm, roundtrip_hbm = roof.pop("decode_hbm_GBps"), roof.pop("roundtrip_hbm_GBps")
+    # every rank's own timing, device and (with --full) fractions, gathered after the timed region (per_rank in the
+    # JSON line)
     my_rec = {"rank": rank, "device": device_ident(torch, dev, local_dev), "name": torch.cuda.get_device_name(dev),
               "groups": G, "encode_ms": round(enc_ms, 4) if do_enc else None, "decode_ms": round(dec_ms, 4),
-              "wall_ms_per_step": round(local_elapsed / args.steps * 1e3, 4),
-              "frac": roof["frac"], "frac_of_ceiling": roof["frac_of_ceiling"],
-              "frac_of_mix_ceiling": roof["frac_of_mix_ceiling"], "read_ceiling": roof["read_ceiling"],
-              "mix_ceiling": roof["mix_ceiling"]}
+              "wall_ms_per_step": round(local_elapsed / args.steps * 1e3, 4)}
+    for key in ("frac", "frac_of_ceiling", "frac_of_mix_ceiling", "read_ceiling", "mix_ceiling"):
+        my_rec[key] = roof[key] if roof else None
     records = [my_rec]
     if world > 1:
         records = [None] * world
@@ -669,11 +743,13 @@ def main():
         "roofline": roof,
         "encode_ms": round(enc_ms, 4) if do_enc else None,
         "decode_ms": round(dec_ms, 4),
-        "decode_hbm_GBps": round(dec_bytes / (dec_ms * 1e-3) / 1e9, 1),
-        "roundtrip_hbm_GBps": round(((enc_bytes if do_enc else 0) + dec_bytes) / ((enc_ms if do_enc else 0) + dec_ms) / 1e6, 1),
-        "recovered_shards_per_step": n_rec_all,
-        "decoded_groups_per_step": n_dec_all,
-        "verified_bit_exact": ok,
+        # what --full adds (None in a plain run, which neither verifies nor measures anything but its steps)
+        "full": bool(args.full),
+        "decode_hbm_GBps": decode_hbm,
+        "roundtrip_hbm_GBps": roundtrip_hbm,
+        "recovered_shards_per_step": n_rec_all if args.full else None,
+        "decoded_groups_per_step": n_dec_all if args.full else None,
+        "verified_bit_exact": ok if args.full else None,
         "cpu_baseline": None,
     }
     if world > 1:
@@ -683,7 +759,7 @@ def main():
         result["combined_digest"] = combine_digests([d for ds in all_digs for d in ds])
     if world > 1:
         dist.barrier()  # every rank is past its GPU work: the CPU leg below cannot perturb any GPU timing
-    if rank == 0 and not args.no_cpu:
+    if rank == 0 and args.full and not args.no_cpu:
         # the reference coder on this node's host cores, in the same run, at every N (north_star): rank 0 only,
         # after the timed region and every rank's ceilings
         try:

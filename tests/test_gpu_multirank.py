@@ -52,7 +52,7 @@ def test_bench_two_ranks_match_single_rank(config):
     if not torch.cuda.is_available():
         pytest.skip("no GPU")
     per_gpu = 4096
-    common = ["--config", config, "--no-cpu", "--steps", "2", "--warmup", "1"]
+    common = ["--config", config, "--full", "--no-cpu", "--steps", "2", "--warmup", "1"]
     two = _run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                 "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), "bench.py", "--gpus", "2",
                 "--groups", str(per_gpu)] + common, parts=2)
@@ -73,7 +73,7 @@ def test_bench_gpus_flag_spawns_the_ranks_itself():
     import torch
     if not torch.cuda.is_available():
         pytest.skip("no GPU")
-    common = ["--config", "20:3", "--no-cpu", "--steps", "2", "--warmup", "1"]
+    common = ["--config", "20:3", "--full", "--no-cpu", "--steps", "2", "--warmup", "1"]
     two = _run([sys.executable, "bench.py", "--gpus", "2", "--groups", "4096"] + common, parts=2)
     one = _run([sys.executable, "bench.py", "--gpus", "1", "--groups", "8192"] + common, parts=2)
     assert two["config"]["ranks"] == 2 and two["verified_bit_exact"]
@@ -89,7 +89,7 @@ def test_bench_eight_ranks_match_single_rank():
     import torch
     if not torch.cuda.is_available():
         pytest.skip("no GPU")
-    common = ["--config", "20:3", "--steps", "2", "--warmup", "1"]
+    common = ["--config", "20:3", "--full", "--steps", "2", "--warmup", "1"]
     # the CPU leg runs at N > 1 too (rank 0, after every rank's GPU work): a small sample here
     eight = _run([sys.executable, "bench.py", "--gpus", "8", "--groups", "2048", "--cpu-seconds", "1",
                   "--cpu-groups", "1024"] + common, parts=8, timeout=300)

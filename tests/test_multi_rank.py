@@ -180,3 +180,34 @@ def test_per_rank_summary():
     assert abs(s["scaling_efficiency"] - 10.0 / 17.0) < 1e-3
     one_dev = [dict(r, device="h0:dev0") for r in recs]  # a rehearsal: every rank on one GPU
     assert bench.per_rank_summary(one_dev, value, payload)["devices"] == 1
+
+
+def test_bench_dump_sample_is_fixed_by_the_arguments():
+    """--dump-outputs: the sampled groups depend on the shapes alone (so two builds dump the same groups), are
+    distinct and sorted, and every rank's float32 arrays together stay under 64 MB for every config and world."""
+    import numpy as np
+    import bench
+    for K, N, B, G, *_ in bench.CONFIGS.values():
+        R = N - K
+        for world in (1, 2, 8):
+            sel = bench.dump_groups(G, R, B, world)
+            assert np.array_equal(sel, bench.dump_groups(G, R, B, world))
+            assert 1 <= len(sel) < G and np.all(np.diff(sel) > 0) and 0 <= sel[0] and sel[-1] < G
+            assert world * len(sel) * (4 * (2 * R * B + R + 1) + 8) <= 64 << 20
+    assert np.array_equal(bench.dump_groups(100, 3, 1440), np.arange(100))  # a small batch is dumped whole
+
+
+def test_bench_options(monkeypatch):
+    """--full and --dump-outputs exist and are off by default; --steps is the number of timed steps, at least 1."""
+    import sys
+    import pytest
+    import bench
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    a = bench.parse()
+    assert (a.steps, a.warmup, a.full, a.dump_outputs) == (7, 2, False, None)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "d"])
+    a = bench.parse()
+    assert a.full is True and a.dump_outputs == "d"
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "0"])
+    with pytest.raises(SystemExit):
+        bench.parse()

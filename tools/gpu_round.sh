@@ -8,10 +8,10 @@ timeout -k 10 900 python -u -m pytest tests -m gpu -x -v --timeout 240 --timeout
 tail -2 $out/gtest.log
 timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $out/smoke.log 2>&1 || { cat $out/smoke.log; exit 1; }
 cat $out/smoke.log
-timeout -k 10 300 python bench.py > $out/bench_203.json 2> $out/bench_203.err || exit 1
-timeout -k 10 300 python bench.py --config 10:3dec > $out/bench_103dec.json 2> $out/bench_103dec.err || exit 1
-timeout -k 10 400 python bench.py --config 200:55 --steps 5 > $out/bench_20055.json 2> $out/bench_20055.err || exit 1
-timeout -k 10 300 python bench.py --config 20:3loss1 > $out/bench_203loss1.json 2> $out/bench_203loss1.err || exit 1
+timeout -k 10 300 python bench.py --full > $out/bench_203.json 2> $out/bench_203.err || exit 1
+timeout -k 10 300 python bench.py --full --config 10:3dec > $out/bench_103dec.json 2> $out/bench_103dec.err || exit 1
+timeout -k 10 400 python bench.py --full --config 200:55 --steps 5 > $out/bench_20055.json 2> $out/bench_20055.err || exit 1
+timeout -k 10 300 python bench.py --full --config 20:3loss1 > $out/bench_203loss1.json 2> $out/bench_203loss1.err || exit 1
 cut -c1-300 $out/bench_*.json
 timeout -k 10 200 python tools/bench_wire.py > $out/wire.json || exit 1
 timeout -k 10 200 python tools/bench_seal.py > $out/seal.json || exit 1
