@@ -17,7 +17,7 @@ namespace kfec {
 //   [4+K4, 4+K4+R*K4)      coef[u][j] row u (u < m) of the inverse decode matrix for missing shard u,
 // with K4 = K rounded up to 4 so that the prep kernel writes whole dwords.  Syndrome form (R <= 8, see
 // write_syn in kfec_kernels.hip): [0] status, [1] m, [2] used-parity bits, [8, 40) present data bits,
-// [40, 40 + 8 RT) the RT rows of the C matrix (RT = R up to 4, else 8; kfec_kernels.hip syn_record_stride).
+// [40, 40 + 8 RT) the RT rows of the C matrix (RT = R up to 7, else 8; kfec_kernels.hip syn_record_stride).
 inline size_t rec_k4(size_t K) { return (K + 3) & ~size_t(3); }
 inline size_t record_stride(size_t K, size_t R)
 {
@@ -28,15 +28,13 @@ inline size_t record_stride(size_t K, size_t R)
 // padding), per-1024-group chunk counts / offsets, then the list of up to G group ids (uint32 each)
 inline size_t decode_list_offset(size_t G, size_t K, size_t R) { return (G * record_stride(K, R) + 255) & ~size_t(255); }
 inline size_t decode_list_chunks(size_t G) { return (G + 1023) / 1024; }
-// Hybrid decode (R in [KFEC_DEC_HYBRID_MIN_R, 8]): both record forms are prepared, the syndrome records after the
+// Hybrid decode (R in [kDecHybridMinR, 8]): both record forms are prepared, the syndrome records after the
 // list (at most 112 bytes per group, RT <= 8), and the device picks the listed syndrome kernel for sparse loss or the
-// coefficient-form MAC for dense loss
-#ifndef KFEC_DEC_HYBRID_MIN_R
-#define KFEC_DEC_HYBRID_MIN_R 4  // R = 7, 8: dense decode 14-22% faster, sparse unchanged (profiles/r06_dec_hybrid_ab.txt);
-                                 // R = 5, 6 with R-row coefficient tiles (KFEC_DEC_MT_MID): 2-16% (r06_dec_mt_mid_ab.txt);
-                                 // R = 4 (KFEC_DEC_MT_SMALL): 6%; R = 3 slower (r06_dec_mt_small_ab.txt)
-#endif
-inline bool decode_hybrid_r(size_t R) { return R >= KFEC_DEC_HYBRID_MIN_R && R <= 8; }
+// coefficient-form MAC for dense loss.
+// R = 7, 8: dense decode 14-22% faster, sparse unchanged (profiles/r06_dec_hybrid_ab.txt); R = 5, 6 with R-row
+// coefficient tiles: 2-16% (r06_dec_mt_mid_ab.txt); R = 4 with a 4-row tile: 6%; R = 3 slower (r06_dec_mt_small_ab.txt)
+constexpr size_t kDecHybridMinR = 4;
+inline bool decode_hybrid_r(size_t R) { return R >= kDecHybridMinR && R <= 8; }
 inline size_t decode_hybrid_syn_offset(size_t G, size_t K, size_t R)
 {
     return (decode_list_offset(G, K, R) + 256 + 4 * decode_list_chunks(G) + 4 * G + 255) & ~size_t(255);

@@ -34,36 +34,14 @@ namespace kfec {
 __constant__ GfTables c_gf = make_gf_tables();
 
 static constexpr int kBlock = 256;
-#ifndef KFEC_MAC_BLOCK
-#define KFEC_MAC_BLOCK 256
-#endif
-static constexpr int kMacBlock = KFEC_MAC_BLOCK;  // workgroup of the flattened MAC kernel
+static constexpr int kMacBlock = 256;  // workgroup of the flattened MAC kernel
+static constexpr int kPD = 4;          // granules per lane in the load pipeline of the 32-byte shape (PD - 1 in flight during a MAC)
+static constexpr int kMacPD = kPD;     // the same for the MAC kernel's 32-byte shape with MT < 8
+static constexpr int kMacMinWaves = 1;  // __launch_bounds__ minimum waves per SIMD of the MAC kernels
+static constexpr int kSynMinWaves = 1;  // the same for the syndrome-form decode kernel
 
-// build-time tuning knobs (tools/ab.py builds variants; the shipped library uses the defaults)
-#ifndef KFEC_MAC_BURST
-#define KFEC_MAC_BURST 2  // encode MAC (MT 3..4): 2 = tables, MACs, next loads as bursts; 1 = loads only; 0 = interleaved
-#endif
-#ifndef KFEC_MAC_PD
-#define KFEC_MAC_PD KFEC_PD  // the same for the MAC kernel's 32-byte shape with MT < 8
-#endif
-#ifndef KFEC_PD
-#define KFEC_PD 4  // granules per lane in the load pipeline of the 32-byte shape (PD - 1 in flight during a MAC)
-#endif
-#ifndef KFEC_SYN_MAX_R
-#define KFEC_SYN_MAX_R 8  // decode in syndrome form up to this R (0: coefficient form always; A/B builds)
-#endif
-#ifndef KFEC_SYN_SMALLK_PD
-#define KFEC_SYN_SMALLK_PD 0  // > 0: granules in flight per lane of the syndrome decode for K <= 12 (A/B knob)
-#endif
-#ifndef KFEC_SYN_MINW
-#define KFEC_SYN_MINW 1  // __launch_bounds__ minimum waves per SIMD of the syndrome-form decode kernel
-#endif
-#ifndef KFEC_EXPAND_EB
-#define KFEC_EXPAND_EB 8  // mac_expand: items per thread whose loads are issued together (1: load-use per item)
-#endif
-#ifndef KFEC_SYN_EARLY
-#define KFEC_SYN_EARLY 1  // syn_kernel: C-table bytes loaded with the record header, expanded after the shard loop
-#endif
+// The only build switches: the arithmetic-free ceiling build (tools/libkfec_arithfree.so, bench.py's ceiling).  Every
+// other former A/B switch is fixed at its shipped value; DESIGN.md lists them ("retired build switches").
 #ifndef KFEC_SYN_XORONLY
 #define KFEC_SYN_XORONLY 0  // ablation (timing only, wrong results): the syndrome MACs as plain XORs, same loads / stores
                             // (1: the E / C table reads kept; 2: no table reads -- the arithmetic-free ceiling build)
@@ -71,78 +49,6 @@ static constexpr int kMacBlock = KFEC_MAC_BLOCK;  // workgroup of the flattened 
 #ifndef KFEC_MAC_XORONLY
 #define KFEC_MAC_XORONLY 0  // ablation (timing only, wrong results): mac_kernel's MACs as plain XORs of the shard granules,
                             // no table reads -- same grid, loads and stores (tools/libkfec_arithfree.so: bench.py's ceiling)
-#endif
-#ifndef KFEC_SYN_TPRE
-#define KFEC_SYN_TPRE 1  // syn_loop: the next shard's E tables loaded into SGPRs one shard ahead (0: at use; A/B knob)
-#endif
-#ifndef KFEC_SYN_PAIR
-#define KFEC_SYN_PAIR 0  // syn_loop: two shards per row step, as KFEC_MAC_PAIR (RT <= 4): bit 0 syn_kernel, bit 1
-                         // syn_list_kernel (A/B knob)
-#endif
-#ifndef KFEC_PREP_FUSED
-#define KFEC_PREP_FUSED 1  // decode_prep_lagrange: denominators and numerators in one pass (0: two loops; A/B knob)
-#endif
-#ifndef KFEC_PREP_COEF2
-#define KFEC_PREP_COEF2 1  // decode_prep_lagrange coefficients from stored column points, no modulo (A/B knob)
-#endif
-#if KFEC_PREP_COEF2 && !KFEC_PREP_FUSED
-#error "KFEC_PREP_COEF2 reads the column points the fused pass (KFEC_PREP_FUSED) stores"
-#endif
-#ifndef KFEC_PREP_PREFETCH
-#define KFEC_PREP_PREFETCH 1  // decode_prep_lagrange loads the next group's present bits one group ahead (A/B knob)
-#endif
-#ifndef KFEC_PREP_WAVE
-#define KFEC_PREP_WAVE 1  // decode_prep_lagrange: one wave per group, four groups per workgroup (0: the workgroup; A/B)
-#endif
-#ifndef KFEC_PREP_WAVE_MINW
-#define KFEC_PREP_WAVE_MINW 4  // the same for one wave per group (4: 128 VGPRs, 16 groups in flight per CU)
-#endif
-#ifndef KFEC_PREP_MINW
-#define KFEC_PREP_MINW 8  // decode_prep_lagrange: minimum waves per SIMD (8: 64 VGPRs, 12 spilled, 3% faster than uncapped)
-#endif
-#ifndef KFEC_SYN_REC_COMPACT
-#define KFEC_SYN_REC_COMPACT 1  // syndrome records of 40 + 8 RT bytes (64 at R = 3: one full line per group)
-#endif
-#ifndef KFEC_SYN_ROWMASK
-#define KFEC_SYN_ROWMASK 1  // listed syndrome decode: 0 every parity row, 1 only the rows the group uses,
-                            // 2 as 1 but single-row groups run a two-row variant (A/B knob)
-#endif
-#ifndef KFEC_MAC_PAIR
-#define KFEC_MAC_PAIR 1  // encode MAC, 8-row tiles (R > 8): two shards per row step, acc ^= c_a x_a ^ c_b x_b as three
-                         // 3-input XORs over the six permutes (instead of 2 x (v_bitop3 + v_xor)), rows outer;
-                         // 200:55 encode 151.1 -> 133.8 ms, 40:20 13.24 -> 11.98 ms (profiles/r06_mac_pair_ab.txt)
-#endif
-#ifndef KFEC_ENC_MT_MID
-#define KFEC_ENC_MT_MID 1  // encode R = 5..7 (32-byte granules): 0 an 8-row tile, 1 an R-row tile with the paired MAC, 2 an
-                           // R-row tile in the plain loop. 1: 20:5 9.30 -> 7.49 ms, 20:6 9.56 -> 8.50, 16:7 8.10 -> 7.86,
-                           // 10:6 5.33 -> 4.94 (2: 4.85 there, slower elsewhere) (profiles/r06_mt_mid_ab.txt)
-#endif
-#ifndef KFEC_MAC_PAIR_SMALL
-#define KFEC_MAC_PAIR_SMALL 1  // the pairing in the encode burst loop (3..4-row tiles): 8:4 encode 3.39 -> 3.33 ms,
-                               // 20:3 and 10:3 unchanged (HBM-bound) (profiles/r06_pair_small_ab.txt)
-#endif
-#ifndef KFEC_DEC_PAIR
-#define KFEC_DEC_PAIR 1  // the same pairing in the T-table decode MAC (8-row tiles): 200:55 decode 151.4 -> 137.5 ms,
-                         // 40:20 14.09 -> 13.30 ms, 20:20 15.50 -> 15.07 ms (profiles/r06_dec_pair_ab.txt)
-#endif
-#ifndef KFEC_PREP_SYN_T
-#define KFEC_PREP_SYN_T 1  // decode_prep_perm's syndrome-record form as its own instantiation (0: runtime flag; A/B knob)
-#endif
-#ifndef KFEC_MINW
-#define KFEC_MINW 1  // __launch_bounds__ minimum waves per SIMD of the MAC kernels
-#endif
-#ifndef KFEC_DEC_FACTORED
-#define KFEC_DEC_FACTORED 1  // R > 8 decode records carry the Lagrange factors, not the m x K coefficients (A/B knob)
-#endif
-#ifndef KFEC_DEC_TTAB
-#define KFEC_DEC_TTAB 1  // coefficient-form decode (R > 8): LDS entries point into one table of all 256 coefficients'
-                         // perm tables (1) instead of holding each coefficient's expanded tables (0; A/B knob)
-#endif
-#ifndef KFEC_DEC_EXPAND2
-#define KFEC_DEC_EXPAND2 1  // factored-record entries by dec_expand_fac (0: the flat-index dec_expand; A/B knob)
-#endif
-#ifndef KFEC_DEC_OFS16
-#define KFEC_DEC_OFS16 1  // T-table decode: each row's table offset read by its own 2-byte LDS read (A/B knob)
 #endif
 
 // ---------------------------------------------------------------------------------------------------
@@ -256,7 +162,7 @@ struct PrepArgs {
     int K, N, R;
     uint32_t rec_stride;
     int syn;       // write syndrome-form records (R <= 8) instead of the coefficient form
-    int factored;  // decode_prep_lagrange: write the factored form (dec_expand rebuilds each coefficient)
+    int factored;  // decode_prep_lagrange: write the factored form (dec_expand_fac rebuilds each coefficient)
     // hybrid decode: the coefficient-form prep exits when the listed syndrome shape takes the launch (syn_listed)
     const uint32_t *skip_listed;
     uint32_t cols, cols_pad;
@@ -267,7 +173,7 @@ __device__ __forceinline__ bool prep_skip(const PrepArgs &a)
     return a.skip_listed && (uint64_t)*a.skip_listed * a.cols_pad < a.G * a.cols;
 }
 
-// Factored coefficient-form record (decode_prep_lagrange for the mac_kernel decode, KFEC_DEC_FACTORED): the
+// Factored coefficient-form record (decode_prep_lagrange for the mac_kernel decode): the
 // m x K coefficients of a group are coef[u][j] = exp(lnum_u - log(xm_u ^ xs_j) - lden_j) (see the prep), so the
 // record keeps the factors -- src[j] (and with it the point xs_j), lden_j, lnum_u and the missing points xm_u --
 // 2 K + 2 R bytes instead of m K: at fec=200:55, 528 bytes per group instead of 11 KB, which the prep no longer
@@ -322,42 +228,12 @@ __device__ __forceinline__ void write_empty(const PrepArgs &a, uint64_t g, uint8
 // t with P_t = K + r (0 for unused rows and for u >= m): rows u < RT are written (the ones the syn kernels
 // read), so the kernels read zeros beyond m.
 // Row tile of the syndrome form (the C rows a syn kernel reads: RT x RT bytes) and the record stride: the
-// header, the present bits and RT rows of C -- 64 bytes at R = 3, one whole line per group
-#ifndef KFEC_SYN_FINAL_ROWS
-#define KFEC_SYN_FINAL_ROWS 1  // syn_list_kernel's final mix at RT 5, 6, 8 with the syndromes outer (260 -> 176 VGPRs at RT
-                               // 8): 1%-loss decode 20:8 3.89 -> 3.44 ms, 20:5 2.18 -> 2.13, 20:6 2.49 -> 2.46; RT 7 measured
-                               // 6% slower and keeps the row order (profiles/r06_syn_final_rows_ab.txt)
-#endif
-#ifndef KFEC_DEC_MT_MID
-#define KFEC_DEC_MT_MID 1  // the hybrid decode's coefficient-form MAC for R = 5..7 as an R-row tile (129-149 VGPRs):
-                           // with the hybrid from R = 5, dense 20:6 11.05 -> 9.87 ms, 10:6 random 5.99 -> 5.00, 16:7
-                           // 9.63 -> 9.19, 20:5 9.06 -> 8.88; sparse unchanged (profiles/r06_dec_mt_mid_ab.txt)
-#endif
-#ifndef KFEC_DEC_MT_SMALL
-#define KFEC_DEC_MT_SMALL 1  // the hybrid decode's coefficient-form MAC for R = 4 as a 4-row tile: dense 8:4 decode 3.97 ->
-                             // 3.72 ms; for R = 3 it was slower than the syndrome kernel (20:3 6.2-6.6 -> 6.7, 10:3 random
-                             // 3.11 -> 3.28), so R = 3 stays syndrome-only (profiles/r06_dec_mt_small_ab.txt)
-#endif
-// the coefficient-form decode MAC reads its tables from T (KFEC_DEC_TTAB) for these row tiles
-__host__ __device__ constexpr bool dec_ttab(int MT)
-{
-    return KFEC_DEC_TTAB && (MT == 8 || (KFEC_DEC_MT_MID && MT >= 5 && MT < 8) || (KFEC_DEC_MT_SMALL && MT == 4));
-}
-#ifndef KFEC_DEC_MT4_WIDE
-#define KFEC_DEC_MT4_WIDE 1  // R > 8 coefficient-form decode in 4-row tiles where they compute fewer rows: 40:20 13.40 ->
-                             // 12.62 ms, 30:20 random 6.97 -> 6.38, 30:12 14.57 -> 12.72, 40:20 at 1% loss 4.58 -> 3.23;
-                             // 200:55 keeps 8-row tiles (profiles/r06_dec_mt4_ab.txt)
-#endif
-#ifndef KFEC_SYN_RT_MID
-#define KFEC_SYN_RT_MID 1  // syndrome decode for R = 5..7: RT = R instead of 8 (166 VGPRs at RT 5, 3 waves per SIMD, against
-                           // RT 8's 256): 20:5 decode 12.83 -> 9.18 ms, 20:6 13.40 -> 11.05, 16:7 11.87 -> 10.90, 10:6
-                           // random 7.31 -> 5.89, 20:6 at 1% loss 3.93 -> 2.53 (profiles/r06_syn_rt_mid_ab.txt)
-#endif
-__host__ __device__ constexpr int syn_rt(int R) { return R <= 4 ? (R > 0 ? R : 1) : (KFEC_SYN_RT_MID && R <= 7 ? R : 8); }
-__host__ __device__ inline size_t syn_record_stride(size_t K, size_t R)
-{
-    return KFEC_SYN_REC_COMPACT ? (size_t)((40 + 8 * syn_rt((int)R) + 15) & ~15) : record_stride(K, R);
-}
+// header, the present bits and RT rows of C -- 64 bytes at R = 3, one whole line per group.
+// RT = R up to 7 (R = 5..7 no longer round up to 8: 166 VGPRs at RT 5, 3 waves per SIMD, against RT 8's 256: 20:5
+// decode 12.83 -> 9.18 ms, 20:6 13.40 -> 11.05, 16:7 11.87 -> 10.90, 10:6 random 7.31 -> 5.89, 20:6 at 1% loss
+// 3.93 -> 2.53; profiles/r06_syn_rt_mid_ab.txt)
+__host__ __device__ constexpr int syn_rt(int R) { return R <= 4 ? (R > 0 ? R : 1) : (R <= 7 ? R : 8); }
+__host__ __device__ inline size_t syn_record_stride(size_t R) { return (size_t)((40 + 8 * syn_rt((int)R) + 15) & ~15); }
 
 template <int MAXM, typename F>
 __device__ __forceinline__ void write_syn(const PrepArgs &a, uint64_t g, int m, const int (&M)[MAXM],
@@ -698,7 +574,7 @@ __device__ __forceinline__ int rank_below(const uint64_t (&b)[4], int s)
     return r;
 }
 
-// General m (fec=200:55 and any m > 8): Lagrange (barycentric) form, one 256-thread workgroup per group.
+// General m (fec=200:55 and any m > 8): Lagrange (barycentric) form, one wave per group.
 //   Every share s is an evaluation of the data polynomial f (deg < K) at the point x_s (x_0 = 0,
 //   x_s = alpha^s: the rows of the reference's Vandermonde matrix, fecpp.cpp:401,467), and the K selected
 //   shares S (fecpp.cpp:528-548) determine f.  So the missing data shard M_u is
@@ -712,8 +588,10 @@ __device__ __forceinline__ int rank_below(const uint64_t (&b)[4], int s)
 //   That is O(K*R + m*R + m*K) table lookups per group, against O(m^3 + m^2*K) byte MACs for Gauss-Jordan
 //   followed by the product with the parity rows (measured at 200:55: 63.8 ms -> see DESIGN.md 5).
 constexpr int kPrepThreads = 256;
+constexpr int kPrepTeam = 64;      // threads that solve one group: one wave, four groups per workgroup at once
+constexpr int kPrepMinWaves = 4;   // __launch_bounds__ minimum waves per SIMD (128 VGPRs, 16 groups in flight per CU)
 
-// The fused pass (KFEC_PREP_FUSED) drops a numerator's excluded term (x_s ^ x_c = 0) by reading log[0], which
+// The fused denominator / numerator pass drops a numerator's excluded term (x_s ^ x_c = 0) by reading log[0], which
 // must therefore be 0 mod 255; and its coefficient exponents index exp[] up to 509 without a modulo, which
 // needs exp[] periodic with period 255 over the doubled table.
 constexpr bool gf_exp_periodic()
@@ -726,33 +604,28 @@ constexpr bool gf_exp_periodic()
 static_assert(make_gf_tables().log[0] % 255 == 0, "decode_prep_lagrange relies on log[0] == 255 (0 mod 255)");
 static_assert(gf_exp_periodic(), "decode_prep_lagrange indexes exp[] up to 509 without reduction");
 
-// TEAM threads solve one group: the whole workgroup (256, barriers between the steps) or one wave (64:
-// four groups per workgroup at once, each wave with its own lists and no workgroup barrier inside the group loop --
-// a wave's LDS operations complete in order, the fences only keep the compiler from reordering them).
-template <int TEAM>
-__global__ void __launch_bounds__(kPrepThreads, TEAM == 64 ? KFEC_PREP_WAVE_MINW : KFEC_PREP_MINW) decode_prep_lagrange(PrepArgs a)
+// One wave (a team of kPrepTeam threads) solves one group: four groups per workgroup at once, each wave with its own
+// lists and no workgroup barrier inside the group loop -- a wave's LDS operations complete in order, the fences only
+// keep the compiler from reordering them.
+__global__ void __launch_bounds__(kPrepThreads, kPrepMinWaves) decode_prep_lagrange(PrepArgs a)
 {
-    static_assert(TEAM == kPrepThreads || TEAM == 64, "a team is the workgroup or one wave");
+    constexpr int TEAM = kPrepTeam;
     constexpr int NT = kPrepThreads / TEAM;  // teams (groups in flight) per workgroup
     __shared__ uint8_t s_exp[512], s_log[256];
     __shared__ uint16_t s_full[256];  // FULL_s mod 255
-    __shared__ uint8_t s_C_all[NT][256];      // ids outside S, ascending
-    __shared__ uint8_t s_xC_all[NT][256];     // their points
+    __shared__ uint8_t s_xC_all[NT][256];     // the points of the ids outside S, ascending
     __shared__ uint8_t s_M_all[NT][256];      // missing data ids, ascending
     __shared__ uint8_t s_P_all[NT][256];      // parity share used for missing rank t: the highest present ids, descending
     __shared__ uint8_t s_src_all[NT][256];    // source share of column j
     __shared__ uint16_t s_lden_all[NT][256];  // log den of the source of column j
     __shared__ uint16_t s_lnum_all[NT][256];  // log num_u without the (x_{M_u} ^ x_i) factor
-    __shared__ uint8_t s_xs_all[NT][256];     // KFEC_PREP_COEF2: the point of column j's source
+    __shared__ uint8_t s_xs_all[NT][256];     // the point of column j's source
     const int K = a.K, N = a.N, R = a.R;
     const int team = threadIdx.x / TEAM, tid = threadIdx.x % TEAM;  // (tid: the thread's index in its team)
-    uint8_t *s_C = s_C_all[team], *s_xC = s_xC_all[team], *s_M = s_M_all[team], *s_P = s_P_all[team];
+    uint8_t *s_xC = s_xC_all[team], *s_M = s_M_all[team], *s_P = s_P_all[team];
     uint8_t *s_src = s_src_all[team], *s_xs = s_xs_all[team];
     uint16_t *s_lden = s_lden_all[team], *s_lnum = s_lnum_all[team];
-    auto team_sync = [&]() {
-        if constexpr (TEAM == kPrepThreads) __syncthreads();
-        else __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-    };
+    auto team_sync = [&]() { __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront"); };
     const int K4 = (K + 3) & ~3, kd = K4 / 4;
     stage_gf(s_exp, s_log);
     __syncthreads();
@@ -766,18 +639,18 @@ __global__ void __launch_bounds__(kPrepThreads, TEAM == 64 ? KFEC_PREP_WAVE_MINW
     }
     __syncthreads();
 
-    // KFEC_PREP_PREFETCH: the next group's present bits are loaded while this group is solved
+    // the next group's present bits are loaded while this group is solved
     const uint64_t g0 = (uint64_t)blockIdx.x * NT + team, gstride = (uint64_t)gridDim.x * NT;
     uint64_t pn[4] = {0, 0, 0, 0};
-    if (KFEC_PREP_PREFETCH && g0 < a.G) {
+    if (g0 < a.G) {
 #pragma unroll
         for (int q = 0; q < 4; ++q) pn[q] = a.present[g0 * 4 + q];
     }
     for (uint64_t g = g0; g < a.G; g += gstride) {
         uint64_t w[4], dm[4], pc[4];
 #pragma unroll
-        for (int q = 0; q < 4; ++q) pc[q] = KFEC_PREP_PREFETCH ? pn[q] : a.present[g * 4 + q];
-        if (KFEC_PREP_PREFETCH && g + gstride < a.G) {
+        for (int q = 0; q < 4; ++q) pc[q] = pn[q];
+        if (g + gstride < a.G) {
 #pragma unroll
             for (int q = 0; q < 4; ++q) pn[q] = a.present[(g + gstride) * 4 + q];
         }
@@ -818,15 +691,10 @@ __global__ void __launch_bounds__(kPrepThreads, TEAM == 64 ? KFEC_PREP_WAVE_MINW
         }
         for (int sid = tid; sid < N; sid += TEAM) {
             const int q = sid >> 6, b = sid & 63;
-            if ((Cb[q] >> b) & 1ull) {
-                const int r = rank_below(Cb, sid);
-                s_C[r] = (uint8_t)sid;
-                s_xC[r] = (uint8_t)xpt(sid);
-            }
+            if ((Cb[q] >> b) & 1ull) s_xC[rank_below(Cb, sid)] = (uint8_t)xpt(sid);
             if (sid < K && ((dm[q] >> b) & 1ull)) s_M[rank_below(dm, sid)] = (uint8_t)sid;
         }
         team_sync();
-#if KFEC_PREP_FUSED
         // the K column denominators and the m numerators are one kind of sum, log FULL_s - sum_c log(x_s ^ x_c),
         // so they are one pass of K + m <= N <= 256 items (one per thread) instead of two loops that wave 0
         // ran back to back; a numerator's excluded term c = M_u has x_s ^ x_c = 0, and log[0] = 255 = 0 mod 255
@@ -840,7 +708,7 @@ __global__ void __launch_bounds__(kPrepThreads, TEAM == 64 ? KFEC_PREP_WAVE_MINW
                 sid = s_M[it - K];
             }
             const uint32_t xs = xpt(sid);
-            if (KFEC_PREP_COEF2 && it < K) s_xs[it] = (uint8_t)xs;
+            if (it < K) s_xs[it] = (uint8_t)xs;
             uint32_t acc = 0;
 #pragma unroll 8
             for (int c = 0; c < R; ++c) acc += s_log[xs ^ s_xC[c]];
@@ -848,25 +716,6 @@ __global__ void __launch_bounds__(kPrepThreads, TEAM == 64 ? KFEC_PREP_WAVE_MINW
             if (it < K) s_lden[it] = v;
             else s_lnum[it - K] = v;
         }
-#else
-        for (int j = tid; j < K; j += TEAM) {
-            const bool miss = (dm[j >> 6] >> (j & 63)) & 1ull;
-            const int i = miss ? (int)s_P[rank_below(dm, j)] : j;
-            s_src[j] = (uint8_t)i;
-            const uint32_t xi = xpt(i);
-            uint32_t acc = 0;
-            for (int c = 0; c < R; ++c) acc += s_log[xi ^ s_xC[c]];
-            s_lden[j] = (uint16_t)((s_full[i] + 255u - acc % 255u) % 255u);
-        }
-        for (int u = tid; u < m; u += TEAM) {
-            const int mu = s_M[u];
-            const uint32_t xm = xpt(mu);
-            uint32_t acc = 0;
-            for (int c = 0; c < R; ++c)
-                if (s_C[c] != mu) acc += s_log[xm ^ s_xC[c]];
-            s_lnum[u] = (uint16_t)((s_full[mu] + 255u - acc % 255u) % 255u);
-        }
-#endif
         team_sync();
         uint32_t *srcw = reinterpret_cast<uint32_t *>(rec + 4);
         if (a.factored) {
@@ -915,15 +764,10 @@ __global__ void __launch_bounds__(kPrepThreads, TEAM == 64 ? KFEC_PREP_WAVE_MINW
             for (int b = 0; b < 4; ++b) {
                 const int j = 4 * d + b;
                 if (j < K) {
-                    int ex;
-                    if (KFEC_PREP_COEF2) {
-                        // one LDS level less (the column's point is stored), and the exponent in [2, 764] brought
-                        // under the 510-entry antilog table by one compare instead of a modulo
-                        ex = ln + 510 - (int)s_log[xm ^ s_xs[j]] - (int)s_lden[j];
-                        ex = ex >= 510 ? ex - 255 : ex;
-                    } else {
-                        ex = (ln + 510 - (int)s_log[xm ^ xpt(s_src[j])] - (int)s_lden[j]) % 255;
-                    }
+                    // one LDS level less (the column's point is stored), and the exponent in [2, 764] brought
+                    // under the 510-entry antilog table by one compare instead of a modulo
+                    int ex = ln + 510 - (int)s_log[xm ^ s_xs[j]] - (int)s_lden[j];
+                    ex = ex >= 510 ? ex - 255 : ex;
                     v |= (uint32_t)s_exp[ex] << (8 * b);
                 }
             }
@@ -962,7 +806,7 @@ struct MacArgs {
     uint32_t JC;            // shards per LDS chunk
     uint32_t gmax;          // group slots per chunk
     uint32_t tiles;         // row tiles of MT output rows
-    uint32_t factored;      // decode: factored records (fac_record_stride), coefficients rebuilt by dec_expand
+    uint32_t factored;      // decode: factored records (fac_record_stride), coefficients rebuilt by dec_expand_fac
     const uint32_t *list_count;  // hybrid decode: the listed groups' count; the kernel exits when the listed shape runs
     uint32_t cols_pad;
 };
@@ -1037,14 +881,17 @@ __device__ __forceinline__ uint32_t gran_off(uint32_t col, uint32_t B)
     return col * 4;
 }
 
+// dwords of the perm tables of `rows` coefficients (5 each), rounded up to whole 16-byte reads
+__host__ __device__ constexpr int table_dwords(int rows) { return ((5 * rows + 3) / 4) * 4; }
+
 template <int MT>
 struct MacLayout {
     static_assert(MT >= 1 && MT <= 16, "row tile");
-    static constexpr int TBL_DW = ((5 * MT + 3) / 4) * 4;  // table dwords per (group, shard): 5 per row
+    static constexpr int TBL_DW = table_dwords(MT);         // table dwords per (group, shard): 5 per row
     static constexpr int ENTRY = 16 + 4 * TBL_DW;          // + 8-byte share pointer, 8 pad
 };
 
-// Coefficient-form decode entries (KFEC_DEC_TTAB): the workgroup's LDS starts with T, the perm tables of all 256
+// Coefficient-form decode entries: the workgroup's LDS starts with T, the perm tables of all 256
 // coefficient values (8-dword stride, built once per workgroup); an entry per (group slot, shard) is the share
 // pointer and, per output row of the tile, the byte offset of its coefficient's table in T (u16).  An entry is
 // 24 bytes instead of 16 + 40 * 4, so every shard of a workgroup's groups fits one expansion (fec=200:55,
@@ -1073,36 +920,25 @@ __device__ __forceinline__ void block_chunk_tile(uint32_t b, uint32_t tiles, uin
     chunk = xcd_tile_chunk(k / tiles, b & 7, gridDim.x / tiles);
 }
 
-// expand coefficients of shards [c0, c0+nj) for group slots [0, ng) into LDS entries
-template <int MT, bool DEC>
-__device__ __forceinline__ void mac_expand(const MacArgs &a, uint8_t *s_ent, uint32_t gfirst, uint32_t ng,
-                                           uint32_t c0, uint32_t nj, uint32_t row0)
+// encode: expand the coefficients of shards [c0, c0+nj) for group slots [0, ng) into LDS entries (the parity rows'
+// perm tables; every group shares them, so the encode passes ng = 1)
+template <int MT>
+__device__ __forceinline__ void mac_expand(const MacArgs &a, uint8_t *s_ent, uint32_t ng, uint32_t c0, uint32_t nj,
+                                           uint32_t row0)
 {
     using L = MacLayout<MT>;
     const uint32_t items = ng * nj * MT;
-    // In batches of EB items per thread whose global loads (coefficient byte, record header, source id) are
-    // all issued before the first is used: one memory latency per batch instead of one per item (the
-    // per-item loop waited for each byte in turn, ~6 round trips per chunk at fec=200:55).
-    constexpr int EB = KFEC_EXPAND_EB;
+    // In batches of EB items per thread whose global loads (the coefficient bytes) are all issued before the
+    // first is used: one memory latency per batch instead of one per item (1: load-use per item).
+    constexpr int EB = 8;
     for (uint32_t e0 = 0; e0 < items; e0 += EB * blockDim.x) {
-        uint32_t cv[EB], sv[EB];
+        uint32_t cv[EB];
 #pragma unroll
         for (int b = 0; b < EB; ++b) {
             const uint32_t e = min(e0 + b * blockDim.x + threadIdx.x, items - 1);  // clamped: loads unconditional
             const uint32_t r = e % MT, q = e / MT;
-            const uint32_t jj = q % nj, gs = q / nj;
-            const uint32_t j = c0 + jj, u = row0 + r;
-            if constexpr (DEC) {
-                const uint32_t K4 = (a.K + 3) & ~3u;
-                const uint8_t *rec = a.rec + (uint64_t)(gfirst + gs) * a.rec_stride;
-                const uint32_t hd = *reinterpret_cast<const uint16_t *>(rec);  // status | m << 8
-                const uint32_t c = rec[4 + K4 + min(u, a.R - 1) * K4 + j];
-                cv[b] = ((hd & 0xFFu) == 0 && u < (hd >> 8)) ? c : 0u;
-                sv[b] = rec[4 + j];
-            } else {
-                cv[b] = u < a.R ? a.enc[(uint64_t)(a.K + u) * a.K + j] : 0u;
-                sv[b] = 0;
-            }
+            const uint32_t j = c0 + q % nj, u = row0 + r;
+            cv[b] = u < a.R ? a.enc[(uint64_t)(a.K + u) * a.K + j] : 0u;
         }
 #pragma unroll
         for (int b = 0; b < EB; ++b) {
@@ -1111,15 +947,6 @@ __device__ __forceinline__ void mac_expand(const MacArgs &a, uint8_t *s_ent, uin
             const uint32_t r = e % MT, q = e / MT;
             const uint32_t jj = q % nj, gs = q / nj;
             uint8_t *ent = s_ent + (gs * a.JC + jj) * L::ENTRY;
-            if constexpr (DEC) {
-                if (r == 0) {
-                    const uint32_t src = sv[b];
-                    const uint64_t g = gfirst + gs;
-                    const uint8_t *p = (src < a.K) ? a.data + (g * a.K + src) * a.pitch
-                                                   : a.parity + (g * a.R + (src - a.K)) * a.pitch;
-                    *reinterpret_cast<const uint8_t **>(ent) = p;
-                }
-            }
             uint32_t t[5];
             gf_perm_tables(cv[b], t);
             uint32_t *tp = reinterpret_cast<uint32_t *>(ent + 16) + 5 * r;
@@ -1147,14 +974,14 @@ __device__ __forceinline__ uint32_t lds_addr(const uint8_t *p)
     return (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) uint8_t *)p;
 }
 
-// entries of shards [c0, c0 + nj) for group slots [0, ng): share pointer + MT u16 offsets into T (KFEC_DEC_OFS16:
+// entries of shards [c0, c0 + nj) for group slots [0, ng): share pointer + MT u16 offsets into T (with
 // T's LDS address tbase added, so each is the address its table is read at)
 template <int MT>
 __device__ __forceinline__ void dec_expand(const MacArgs &a, uint8_t *s_ent, uint32_t gfirst, uint32_t ng, uint32_t c0,
-                                           uint32_t nj, uint32_t row0, const uint8_t *s_exp, const uint8_t *s_log,
-                                           uint32_t tbase)
+                                           uint32_t nj, uint32_t row0, uint32_t tbase)
 {
     static_assert(MT >= 1 && MT <= 8, "entry: 8 offsets (rows past MT take the zero table)");
+    // (plain coefficient records only: factored records go to dec_expand_fac)
     const uint32_t items = ng * nj, K4 = (a.K + 3) & ~3u;
     constexpr int EB = 4;  // entries per thread whose loads are issued together
     for (uint32_t e0 = 0; e0 < items; e0 += EB * blockDim.x) {
@@ -1166,21 +993,8 @@ __device__ __forceinline__ void dec_expand(const MacArgs &a, uint8_t *s_ent, uin
             const uint8_t *rec = a.rec + (uint64_t)(gfirst + gs) * a.rec_stride;
             hd[b] = *reinterpret_cast<const uint16_t *>(rec);  // status | m << 8
             sv[b] = rec[4 + j];
-            if (a.factored) {
-                const uint32_t L0 = fac_lnum_off(a.K), R8 = fac_r8(a.R);
-                const uint2 ln = *reinterpret_cast<const uint2 *>(rec + L0 + row0);  // (row0 % 8 == 0, rows < R8)
-                const uint2 xm = *reinterpret_cast<const uint2 *>(rec + L0 + R8 + row0);
-                const uint32_t ld = rec[4 + K4 + j];
 #pragma unroll
-                for (int r = 0; r < MT; ++r) {
-                    const uint32_t lnr = ((r < 4 ? ln.x : ln.y) >> (8 * (r & 3))) & 0xFFu;
-                    const uint32_t xmr = ((r < 4 ? xm.x : xm.y) >> (8 * (r & 3))) & 0xFFu;
-                    cv[b][r] = lnr | (xmr << 8) | (ld << 16);  // (combined below, after every load is issued)
-                }
-            } else {
-#pragma unroll
-                for (int r = 0; r < MT; ++r) cv[b][r] = rec[4 + K4 + min(row0 + r, a.R - 1) * K4 + j];
-            }
+            for (int r = 0; r < MT; ++r) cv[b][r] = rec[4 + K4 + min(row0 + r, a.R - 1) * K4 + j];
         }
 #pragma unroll
         for (int b = 0; b < EB; ++b) {
@@ -1194,19 +1008,6 @@ __device__ __forceinline__ void dec_expand(const MacArgs &a, uint8_t *s_ent, uin
             *reinterpret_cast<const uint8_t **>(ent) = p;
             const bool ok = (hd[b] & 0xFFu) == 0;
             const uint32_t m = hd[b] >> 8;
-            // the tile's coefficients of (group, column j) from the record's factors: exp(lnum_u - log(xm_u ^ xs_j)
-            // - lden_j), two lookups each in the workgroup's GF tables; the exponent in [1, 764] is brought under the
-            // doubled antilog table by one compare (as the prep does)
-            if (a.factored) {
-                const uint32_t xs = src ? (uint32_t)s_exp[src] : 0u;  // the point of the column's share (x_0 = 0)
-#pragma unroll
-                for (int r = 0; r < MT; ++r) {
-                    const uint32_t v = cv[b][r];
-                    int ex = (int)(v & 0xFFu) + 510 - (int)s_log[((v >> 8) & 0xFFu) ^ xs] - (int)(v >> 16);
-                    ex = ex >= 510 ? ex - 255 : ex;
-                    cv[b][r] = s_exp[ex];
-                }
-            }
             uint32_t o[8];
 #pragma unroll
             for (int r = 0; r < 8; ++r) o[r] = tbase + ((r < MT && ok && row0 + r < m) ? cv[b][r < MT ? r : 0] * 32u : 0u);  // T[0] = zero tables
@@ -1217,7 +1018,7 @@ __device__ __forceinline__ void dec_expand(const MacArgs &a, uint8_t *s_ent, uin
     }
 }
 
-// dec_expand for factored records (KFEC_DEC_EXPAND2): one column per thread (nj <= K < 256 = the workgroup),
+// dec_expand for factored records: one column per thread (nj <= K < 256 = the workgroup),
 // groups in batches of four whose two per-column bytes (src, lden) are loaded together; a group's header and the
 // tile's 8 lnum / xm bytes are uniform (scalar loads), and each coefficient's T address is one lookup of its
 // exponent in s_taddr -- no division of the flat entry index, no per-entry header loads, no exponent fold.
@@ -1280,17 +1081,21 @@ __device__ __forceinline__ void dec_expand_fac(const MacArgs &a, uint8_t *s_ent,
 // next group, so a wave-instruction reads 2 KiB of one shard row (V = 32).  One workgroup per 256 items
 // (non-persistent grid: the dispatcher refills each CU as workgroups retire).  Per lane: K loads of V bytes
 // (PD in flight), MT accumulator rows, MT stores.
+// DEC: the coefficient-form decode, always with T-table entries (kDecEntry) and row tiles of 4..8 rows.
 template <int VEC, int MT, bool DEC, int PDX = 0>
-__global__ void __launch_bounds__(kMacBlock, KFEC_MINW) mac_kernel(MacArgs a)
+__global__ void __launch_bounds__(kMacBlock, kMacMinWaves) mac_kernel(MacArgs a)
 {
+    static_assert(!DEC || (MT >= 4 && MT <= 8), "decode row tiles (launch_decode)");
     using L = MacLayout<MT>;
     constexpr int W = Gran<VEC>::W;
     // shards in flight per lane (~64 B per lane); PDX: the latency shape (a handful of groups, often read
     // straight from pinned host memory) keeps many more loads in flight so the PCIe round trips overlap
-    // (MT = 8, the VALU-bound tall tiles: 2, to keep 3 waves per SIMD)
-    constexpr bool PAIRED = !DEC && (MT >= 8 || (KFEC_ENC_MT_MID == 1 && MT >= 5));
-    constexpr int PD = PDX ? PDX : (VEC >= 32 ? (MT >= 8 || PAIRED || (DEC && dec_ttab(MT)) ? 2 : KFEC_MAC_PD)
-                                               : 2 * KFEC_PD);
+    // (MT = 8, the VALU-bound tall tiles: 2, to keep 3 waves per SIMD).
+    // PAIRED: the encode's tiles of 5 or more rows take two shards per row step (below).  R-row tile for R = 5..7
+    // instead of an 8-row one: 20:5 9.30 -> 7.49 ms, 20:6 9.56 -> 8.50, 16:7 8.10 -> 7.86, 10:6 5.33 -> 4.94 (the
+    // R-row tile in the plain loop: 4.85 there, slower elsewhere) (profiles/r06_mt_mid_ab.txt)
+    constexpr bool PAIRED = !DEC && MT >= 5;
+    constexpr int PD = PDX ? PDX : (VEC >= 32 ? (PAIRED || DEC ? 2 : kMacPD) : 2 * kPD);
     constexpr int VB = VEC >= 4 ? VEC : 4;  // bytes per granule
     extern __shared__ __attribute__((aligned(16))) uint8_t s_ent[];
 
@@ -1304,25 +1109,21 @@ __global__ void __launch_bounds__(kMacBlock, KFEC_MINW) mac_kernel(MacArgs a)
     const uint32_t row0 = tile * MT;
     const uint32_t K = a.K, cols = a.cols;
     const bool enc_once = !DEC && K <= a.JC;
-    constexpr bool ttab = DEC && dec_ttab(MT);
     uint8_t *s_T = s_ent;
-    // ttab: T, then (factored records) the GF exp / log tables, then the entries
-    constexpr uint32_t kGfBytes = ttab ? kDecGfBytes : 0u;
+    // decode: T, then (factored records) the GF exp / log tables, then the entries
     uint8_t *s_gexp = s_ent + kTBytes, *s_glog = s_gexp + 512;
     uint16_t *s_taddr = reinterpret_cast<uint16_t *>(s_gexp + 768);
-    uint8_t *s_E = ttab ? s_ent + kTBytes + kGfBytes : s_ent;  // entries (after T)
+    uint8_t *s_E = DEC ? s_ent + kTBytes + kDecGfBytes : s_ent;  // entries (after T)
     if (enc_once) {
-        mac_expand<MT, false>(a, s_ent, 0, 1, 0, K, row0);
+        mac_expand<MT>(a, s_ent, 1, 0, K, row0);
         __syncthreads();
     }
-    if constexpr (ttab) {
+    if constexpr (DEC) {
         dec_build_t(s_T);  // (ordered by the first chunk's barrier below)
         if (a.factored) {
             stage_gf(s_gexp, s_glog);
-            if (KFEC_DEC_EXPAND2) {
-                const uint32_t tb = KFEC_DEC_OFS16 ? lds_addr(s_T) : 0u;
-                for (uint32_t i = threadIdx.x; i < 768; i += blockDim.x) s_taddr[i] = (uint16_t)(tb + 32u * c_gf.exp[i % 255u]);
-            }
+            const uint32_t tb = lds_addr(s_T);
+            for (uint32_t i = threadIdx.x; i < 768; i += blockDim.x) s_taddr[i] = (uint16_t)(tb + 32u * c_gf.exp[i % 255u]);
         }
     }
     const uint32_t item = base + threadIdx.x;
@@ -1355,19 +1156,19 @@ __global__ void __launch_bounds__(kMacBlock, KFEC_MINW) mac_kernel(MacArgs a)
     for (uint32_t c0 = 0; c0 < K; c0 += a.JC) {
         const uint32_t nj = min(a.JC, K - c0);
         if (!enc_once) {
-            // (ttab: T is read only after the expansion's barrier; the factored form's GF tables are read by the
-            // expansion itself -- dec_expand_fac waits for them after issuing its loads, dec_expand here)
-            if (!ttab || c0 > 0 || (a.factored && !KFEC_DEC_EXPAND2)) __syncthreads();
-            if constexpr (ttab) {
-                const uint32_t tb = KFEC_DEC_OFS16 ? lds_addr(s_T) : 0u;
-                if (KFEC_DEC_EXPAND2 && a.factored) dec_expand_fac<MT>(a, s_E, gfirst, ng, c0, nj, row0, s_gexp, s_glog, s_taddr, tb, c0 == 0);
-                else dec_expand<MT>(a, s_E, gfirst, ng, c0, nj, row0, s_gexp, s_glog, tb);
+            // (decode: T is read only after the expansion's barrier; the factored form's GF tables are read by the
+            // expansion itself -- dec_expand_fac waits for them after issuing its loads)
+            if (!DEC || c0 > 0) __syncthreads();
+            if constexpr (DEC) {
+                const uint32_t tb = lds_addr(s_T);
+                if (a.factored) dec_expand_fac<MT>(a, s_E, gfirst, ng, c0, nj, row0, s_gexp, s_glog, s_taddr, tb, c0 == 0);
+                else dec_expand<MT>(a, s_E, gfirst, ng, c0, nj, row0, tb);
             }
-            else mac_expand<MT, DEC>(a, s_ent, gfirst, DEC ? ng : 1u, c0, nj, row0);
+            else mac_expand<MT>(a, s_ent, 1u, c0, nj, row0);
             __syncthreads();
         }
         if (rows == 0) continue;
-        constexpr uint32_t ENT = ttab ? kDecEntry : L::ENTRY;
+        constexpr uint32_t ENT = DEC ? kDecEntry : L::ENTRY;
         const uint8_t *ent0 = s_E + (gs * a.JC) * ENT;
         auto share_ptr = [&](uint32_t jj) -> const uint8_t * {
             if constexpr (DEC) {
@@ -1376,51 +1177,36 @@ __global__ void __launch_bounds__(kMacBlock, KFEC_MINW) mac_kernel(MacArgs a)
                 return enc_base + (uint64_t)(c0 + jj) * a.pitch;
             }
         };
-        // ttab: the T offsets of a shard are read one shard ahead, so the table reads of the shard being
-        // multiplied depend on no LDS read still in flight.  KFEC_DEC_OFS16: one ds_read_u16 per row straight
-        // into the register that addresses its table (no extraction op per row and shard: 8 of ~370 VALU ops)
-        // instead of two 8-byte reads and a word-select add per row
-        uint64_t ofs_lo = 0, ofs_hi = 0;
+        // decode: the T offsets of a shard are read one shard ahead, so the table reads of the shard being
+        // multiplied depend on no LDS read still in flight: one ds_read_u16 per row straight into the register that
+        // addresses its table (no extraction op per row and shard: 8 of ~370 VALU ops) instead of two 8-byte reads
+        // and a word-select add per row
         uint32_t ofs16[MT];
         auto read_ofs = [&](uint32_t jj) {
-            if constexpr (ttab) {
-                if constexpr (KFEC_DEC_OFS16) {
-                    // (volatile: kept as separate 2-byte reads, not merged into one wide read and split by VALU)
-                    typedef const volatile __attribute__((address_space(3))) uint16_t lds_u16;
-                    const lds_u16 *q = (const lds_u16 *)(ent0 + min(jj, nj - 1) * ENT + 8);
+            if constexpr (DEC) {
+                // (volatile: kept as separate 2-byte reads, not merged into one wide read and split by VALU)
+                typedef const volatile __attribute__((address_space(3))) uint16_t lds_u16;
+                const lds_u16 *q = (const lds_u16 *)(ent0 + min(jj, nj - 1) * ENT + 8);
 #pragma unroll
-                    for (int r = 0; r < MT; ++r) ofs16[r] = q[r];
-                } else {
-                    const uint64_t *q = reinterpret_cast<const uint64_t *>(ent0 + min(jj, nj - 1) * ENT + 8);
-                    ofs_lo = q[0];
-                    ofs_hi = q[1];
-                }
+                for (int r = 0; r < MT; ++r) ofs16[r] = q[r];
             }
         };
         auto mac = [&](const Gran<VEC> &cur, uint32_t jj) {
             uint32_t t[L::TBL_DW];
-            if constexpr (ttab) {
-                const uint64_t lo = ofs_lo, hi = ofs_hi;
+            if constexpr (DEC) {
                 uint32_t oc[MT];
 #pragma unroll
-                for (int r = 0; r < MT; ++r) oc[r] = KFEC_DEC_OFS16 ? ofs16[r] : 0u;
+                for (int r = 0; r < MT; ++r) oc[r] = ofs16[r];
                 read_ofs(jj + 1);
 #pragma unroll
                 for (int r = 0; r < MT; ++r) {
-                    const uint32_t o = KFEC_DEC_OFS16 ? oc[r] : (uint32_t)((r < 4 ? lo : hi) >> (16 * (r & 3))) & 0xFFFFu;
-                    if constexpr (KFEC_DEC_OFS16) {  // o: the table's LDS address (dec_expand added T's base)
-                        typedef unsigned int v4u __attribute__((ext_vector_type(4)));
-                        typedef const __attribute__((address_space(3))) v4u lds_u4;
-                        typedef const __attribute__((address_space(3))) uint32_t lds_u32;
-                        const v4u q = *(const lds_u4 *)(uintptr_t)o;
-                        t[5 * r] = q.x; t[5 * r + 1] = q.y; t[5 * r + 2] = q.z; t[5 * r + 3] = q.w;
-                        t[5 * r + 4] = *(const lds_u32 *)(uintptr_t)(o + 16);
-                    } else {
-                        const uint8_t *te = s_T + o;
-                        const uint4 q = *reinterpret_cast<const uint4 *>(te);
-                        t[5 * r] = q.x; t[5 * r + 1] = q.y; t[5 * r + 2] = q.z; t[5 * r + 3] = q.w;
-                        t[5 * r + 4] = *reinterpret_cast<const uint32_t *>(te + 16);
-                    }
+                    const uint32_t o = oc[r];  // the table's LDS address (the expansion added T's base)
+                    typedef unsigned int v4u __attribute__((ext_vector_type(4)));
+                    typedef const __attribute__((address_space(3))) v4u lds_u4;
+                    typedef const __attribute__((address_space(3))) uint32_t lds_u32;
+                    const v4u q = *(const lds_u4 *)(uintptr_t)o;
+                    t[5 * r] = q.x; t[5 * r + 1] = q.y; t[5 * r + 2] = q.z; t[5 * r + 3] = q.w;
+                    t[5 * r + 4] = *(const lds_u32 *)(uintptr_t)(o + 16);
                 }
             } else {
                 const uint4 *tv = reinterpret_cast<const uint4 *>(ent0 + jj * ENT + 16);
@@ -1448,7 +1234,7 @@ __global__ void __launch_bounds__(kMacBlock, KFEC_MINW) mac_kernel(MacArgs a)
         read_ofs(0);
         uint32_t jb = 0;
         for (; jb + PD <= nj; jb += PD) {
-            if constexpr (!DEC && MT >= 3 && MT <= 4 && VEC >= 32 && KFEC_MAC_BURST == 2) {
+            if constexpr (!DEC && MT >= 3 && MT <= 4 && VEC >= 32) {
                 // every table of the PD granules first (one LDS burst), the PD MACs, then the next PD
                 // granules' loads as one burst: 129 VGPRs at MT = 3 (3 waves per SIMD, from 98 and 5); encode
                 // 20:3 2.2% and 8:4 4% faster, 10:3 within 1%, in an interleaved A/B (profiles/r05_enc_burst_ab.txt;
@@ -1464,7 +1250,9 @@ __global__ void __launch_bounds__(kMacBlock, KFEC_MINW) mac_kernel(MacArgs a)
                         tt[u][4 * i] = q.x; tt[u][4 * i + 1] = q.y; tt[u][4 * i + 2] = q.z; tt[u][4 * i + 3] = q.w;
                     }
                 }
-                if constexpr (KFEC_MAC_PAIR_SMALL && !KFEC_MAC_XORONLY && PD % 2 == 0) {
+                if constexpr (!KFEC_MAC_XORONLY && PD % 2 == 0) {
+                    // two shards per row step, as the tall tiles below: 8:4 encode 3.39 -> 3.33 ms, 20:3 and 10:3
+                    // unchanged (HBM-bound) (profiles/r06_pair_small_ab.txt)
 #pragma unroll
                     for (int u = 0; u < PD; u += 2) {
 #pragma unroll
@@ -1502,10 +1290,12 @@ __global__ void __launch_bounds__(kMacBlock, KFEC_MINW) mac_kernel(MacArgs a)
                 }
 #pragma unroll
                 for (int u = 0; u < PD; ++u) x[u] = load_gran<VEC>(share_ptr(min(jb + u + PD, nj - 1)), col, a.B);
-            } else if constexpr (PAIRED && VEC >= 32 && PD == 2 && KFEC_MAC_PAIR && !KFEC_MAC_XORONLY) {
-                // the two shards of the trip together, row by row: 6 permutes and three 3-input XORs per row and dword
-                // (one VALU op fewer than two separate MACs); the selectors of both granules stay live across the
-                // rows, each row's two tables are read from LDS just before use (not all 8 rows' at once)
+            } else if constexpr (PAIRED && VEC >= 32 && PD == 2 && !KFEC_MAC_XORONLY) {
+                // the paired MAC (formerly KFEC_MAC_PAIR): the two shards of the trip together, row by row, acc ^=
+                // c_a x_a ^ c_b x_b as 6 permutes and three 3-input XORs per row and dword (one VALU op fewer than two
+                // separate MACs of v_bitop3 + v_xor); the selectors of both granules stay live across the rows, each
+                // row's two tables are read from LDS just before use (not all 8 rows' at once); 200:55 encode 151.1 ->
+                // 133.8 ms, 40:20 13.24 -> 11.98 ms (profiles/r06_mac_pair_ab.txt)
                 uint32_t sa[W][3], sb[W][3];
 #pragma unroll
                 for (int w = 0; w < W; ++w) {
@@ -1536,9 +1326,10 @@ __global__ void __launch_bounds__(kMacBlock, KFEC_MINW) mac_kernel(MacArgs a)
                 }
 #pragma unroll
                 for (int u = 0; u < PD; ++u) x[u] = load_gran<VEC>(share_ptr(min(jb + u + PD, nj - 1)), col, a.B);
-            } else if constexpr (DEC && ttab && KFEC_DEC_OFS16 && VEC >= 32 && PD == 2 && KFEC_DEC_PAIR && !KFEC_MAC_XORONLY) {
+            } else if constexpr (DEC && VEC >= 32 && PD == 2 && !KFEC_MAC_XORONLY) {
                 // the decode's form of the same pairing: each row's two tables are read from T at the addresses the
-                // two entries hold (dec_expand added T's base)
+                // two entries hold (the expansion added T's base); 200:55 decode 151.4 -> 137.5 ms, 40:20 14.09 ->
+                // 13.30 ms, 20:20 15.50 -> 15.07 ms (profiles/r06_dec_pair_ab.txt)
                 typedef const volatile __attribute__((address_space(3))) uint16_t lds_u16;
                 typedef unsigned int v4u __attribute__((ext_vector_type(4)));
                 typedef const __attribute__((address_space(3))) v4u lds_u4;
@@ -1577,12 +1368,6 @@ __global__ void __launch_bounds__(kMacBlock, KFEC_MINW) mac_kernel(MacArgs a)
                 }
 #pragma unroll
                 for (int u = 0; u < PD; ++u) x[u] = load_gran<VEC>(share_ptr(min(jb + u + PD, nj - 1)), col, a.B);
-            } else if constexpr (!DEC && KFEC_MAC_BURST == 1) {
-                // the PD granules' MACs, then the next PD granules' loads as one burst
-#pragma unroll
-                for (int u = 0; u < PD; ++u) mac(x[u], jb + u);
-#pragma unroll
-                for (int u = 0; u < PD; ++u) x[u] = load_gran<VEC>(share_ptr(min(jb + u + PD, nj - 1)), col, a.B);
             } else {
 #pragma unroll
                 for (int u = 0; u < PD; ++u) {
@@ -1593,7 +1378,7 @@ __global__ void __launch_bounds__(kMacBlock, KFEC_MINW) mac_kernel(MacArgs a)
                 }
             }
         }
-        if constexpr (DEC && ttab && KFEC_DEC_OFS16 && VEC >= 32 && PD == 2 && KFEC_DEC_PAIR && !KFEC_MAC_XORONLY)
+        if constexpr (DEC && VEC >= 32 && PD == 2 && !KFEC_MAC_XORONLY)
             read_ofs(jb);  // (the paired loop read its offsets itself: the tail's MAC takes shard jb's)
 #pragma unroll
         for (int u = 0; u < PD; ++u)
@@ -1638,7 +1423,7 @@ struct SynArgs {
 
 template <int RT>
 struct SynLayout {
-    static constexpr int TD = ((5 * RT + 3) / 4) * 4;  // table dwords per (group, output row u): RT tables
+    static constexpr int TD = table_dwords(RT);  // table dwords per (group, output row u): RT tables
 };
 
 typedef unsigned int u32x4v __attribute__((ext_vector_type(4)));
@@ -1697,7 +1482,7 @@ __device__ __forceinline__ void syn_expand_one(const uint8_t *rec, uint32_t ur, 
 // A group that lost m data shards uses m parity rows: syn_list_kernel (one group per task, so the mask is
 // uniform) leaves out the rows its group does not use -- at ~1% loss mostly 2 of 3 (fec=20:3 listed decode
 // 1.41 -> 1.23 ms, profiles/r04_rowmask_ab.txt).
-template <int VEC, int RT, int PD, uint32_t ROWS = (1u << RT) - 1u, bool PAIR = (KFEC_SYN_PAIR & 1) != 0>
+template <int VEC, int RT, int PD, uint32_t ROWS = (1u << RT) - 1u>
 __device__ __forceinline__ void syn_loop(const SynArgs &a, uint32_t (&acc)[RT][Gran<VEC>::W], __amdgpu_buffer_rsrc_t rd,
                                          __amdgpu_buffer_rsrc_t rp, uint32_t drow, uint32_t prow, uint32_t used,
                                          uint64_t p0, const uint8_t *rec)
@@ -1718,24 +1503,18 @@ __device__ __forceinline__ void syn_loop(const SynArgs &a, uint32_t (&acc)[RT][G
         return ((wq >> (j & 63u)) & 1ull) ? drow + j * pitch : kAbsent;
     };
     typedef const __attribute__((address_space(4))) uint32_t cu32;  // uniform: scalar loads into SGPRs
-    uint32_t tn[5 * RT];  // KFEC_SYN_TPRE: shard j's tables, loaded while shard j - 1 is multiplied
+    uint32_t tn[5 * RT];  // shard j's tables, loaded into SGPRs while shard j - 1 is multiplied
     auto tload = [&](uint32_t j) {
         const cu32 *tg = (const cu32 *)(a.etab + (size_t)min(j, K - 1) * a.etab_rows * 5);
 #pragma unroll
         for (int i = 0; i < 5 * RT; ++i) tn[i] = tg[i];
     };
-    if (KFEC_SYN_TPRE) tload(0);
+    tload(0);
     auto mac = [&](const Gran<VEC> &cur, uint32_t j) {
         uint32_t t[5 * RT];
-        if (KFEC_SYN_TPRE) {
 #pragma unroll
-            for (int i = 0; i < 5 * RT; ++i) t[i] = tn[i];
-            tload(j + 1);
-        } else {
-            const cu32 *tg = (const cu32 *)(a.etab + (size_t)j * a.etab_rows * 5);
-#pragma unroll
-            for (int i = 0; i < 5 * RT; ++i) t[i] = tg[i];
-        }
+        for (int i = 0; i < 5 * RT; ++i) t[i] = tn[i];
+        tload(j + 1);
 #pragma unroll
         for (int w = 0; w < W; ++w) {
             const uint32_t xv = cur.d[w];
@@ -1754,53 +1533,8 @@ __device__ __forceinline__ void syn_loop(const SynArgs &a, uint32_t (&acc)[RT][G
 #pragma unroll
     for (int u = 0; u < PD; ++u) x[u] = bload<VEC>(rd, dofs(min((uint32_t)u, K - 1)));
     uint32_t jb = 0;
-    if constexpr (PAIR && KFEC_SYN_TPRE && !KFEC_SYN_XORONLY && PD % 2 == 0 && RT <= 4) {
-        // two shards per row step (mac_kernel's KFEC_MAC_PAIR): both shards' tables prefetched one pair ahead
-        uint32_t tm[5 * RT];
-        auto tload2 = [&](uint32_t j) {
-            tload(j);
-            const cu32 *tg = (const cu32 *)(a.etab + (size_t)min(j + 1, K - 1) * a.etab_rows * 5);
-#pragma unroll
-            for (int i = 0; i < 5 * RT; ++i) tm[i] = tg[i];
-        };
-        tload2(0);
-        for (; jb + PD <= K; jb += PD) {
-#pragma unroll
-            for (int u = 0; u < PD; u += 2) {
-                uint32_t ta[5 * RT], tb[5 * RT];
-#pragma unroll
-                for (int i = 0; i < 5 * RT; ++i) {
-                    ta[i] = tn[i];
-                    tb[i] = tm[i];
-                }
-                tload2(jb + u + 2);
-#pragma unroll
-                for (int w = 0; w < W; ++w) {
-                    const uint32_t xa = x[u].d[w], xb = x[u + 1].d[w];
-                    const uint32_t sa0 = xa & 0x07070707u, sa1 = (xa >> 3) & 0x07070707u, sa2 = (xa >> 6) & 0x03030303u;
-                    const uint32_t sb0 = xb & 0x07070707u, sb1 = (xb >> 3) & 0x07070707u, sb2 = (xb >> 6) & 0x03030303u;
-#pragma unroll
-                    for (int r = 0; r < RT; ++r) {
-                        if (!((ROWS >> r) & 1u)) continue;
-                        const uint32_t *pa = ta + 5 * r, *pb = tb + 5 * r;
-                        const uint32_t a0 = __builtin_amdgcn_perm(pa[1], pa[0], sa0);
-                        const uint32_t a1 = __builtin_amdgcn_perm(pa[3], pa[2], sa1);
-                        const uint32_t a2 = __builtin_amdgcn_perm(pa[4], pa[4], sa2);
-                        const uint32_t b0 = __builtin_amdgcn_perm(pb[1], pb[0], sb0);
-                        const uint32_t b1 = __builtin_amdgcn_perm(pb[3], pb[2], sb1);
-                        const uint32_t b2 = __builtin_amdgcn_perm(pb[4], pb[4], sb2);
-                        acc[r][w] = xor3(xor3(xor3(acc[r][w], a0, a1), a2, b0), b1, b2);
-                    }
-                }
-                x[u] = bload<VEC>(rd, dofs(min(jb + u + PD, K - 1)));
-                x[u + 1] = bload<VEC>(rd, dofs(min(jb + u + 1 + PD, K - 1)));
-            }
-        }
-        tload(jb);  // the tail's single MACs take their tables through tn, shard jb first
-    } else
     for (; jb + PD <= K; jb += PD) {
-        // (the encode's burst order, KFEC_MAC_BURST, measured slower here, also at 3 or 2 waves per SIMD:
-        // profiles/r05_syn_burst_ab.txt)
+        // (the encode's burst order measured slower here, also at 3 or 2 waves per SIMD: profiles/r05_syn_burst_ab.txt)
 #pragma unroll
         for (int u = 0; u < PD; ++u) {
             mac(x[u], jb + u);
@@ -1821,8 +1555,10 @@ __device__ __forceinline__ void syn_final(const SynArgs &a, const uint32_t (&acc
     constexpr int TD = SynLayout<RT>::TD;
     const uint64_t obase = ((uint64_t)g * a.R) * a.pitch + off;
     if constexpr (OUTER && RT >= 5 && RT != 7 && !KFEC_SYN_XORONLY) {
-        // syndromes outer: y_r's selectors once per r, its contribution to every output row, then y_r is dead --
-        // the output-row order below keeps all RT x W x 3 selectors live (192 VGPRs at RT 8)
+        // syndromes outer (syn_list_kernel's final mix at RT 5, 6, 8): y_r's selectors once per r, its contribution to
+        // every output row, then y_r is dead -- the output-row order below keeps all RT x W x 3 selectors live (260 ->
+        // 176 VGPRs at RT 8): 1%-loss decode 20:8 3.89 -> 3.44 ms, 20:5 2.18 -> 2.13, 20:6 2.49 -> 2.46; RT 7 measured
+        // 6% slower and keeps the row order (profiles/r06_syn_final_rows_ab.txt)
         uint32_t o[RT][W];
 #pragma unroll
         for (int u = 0; u < RT; ++u)
@@ -1887,18 +1623,15 @@ __device__ __forceinline__ void syn_final(const SynArgs &a, const uint32_t (&acc
 template <int RT, typename F>
 __device__ __forceinline__ void by_row_mask(uint32_t rows, F &&f)
 {
-    // KFEC_SYN_ROWMASK 2: single-row waves take a two-row variant (fewer registers)
-    constexpr uint32_t one0 = KFEC_SYN_ROWMASK == 1 ? 1u : 3u, one1 = KFEC_SYN_ROWMASK == 1 ? 2u : 3u,
-                       one2 = KFEC_SYN_ROWMASK == 1 ? 4u : 5u;
-    if constexpr (RT == 2 && KFEC_SYN_ROWMASK != 0) {
-        if (rows == 1) return f(std::integral_constant<uint32_t, one0>());
-        if (rows == 2) return f(std::integral_constant<uint32_t, one1>());
-    } else if constexpr (RT == 3 && KFEC_SYN_ROWMASK != 0) {
+    if constexpr (RT == 2) {
+        if (rows == 1) return f(std::integral_constant<uint32_t, 1>());
+        if (rows == 2) return f(std::integral_constant<uint32_t, 2>());
+    } else if constexpr (RT == 3) {
         switch (rows) {
-        case 1: return f(std::integral_constant<uint32_t, one0>());
-        case 2: return f(std::integral_constant<uint32_t, one1>());
+        case 1: return f(std::integral_constant<uint32_t, 1>());
+        case 2: return f(std::integral_constant<uint32_t, 2>());
         case 3: return f(std::integral_constant<uint32_t, 3>());
-        case 4: return f(std::integral_constant<uint32_t, one2>());
+        case 4: return f(std::integral_constant<uint32_t, 4>());
         case 5: return f(std::integral_constant<uint32_t, 5>());
         case 6: return f(std::integral_constant<uint32_t, 6>());
         default: break;
@@ -1925,7 +1658,7 @@ template <int VEC, int RT, int PDX = 0>
 __global__ void __launch_bounds__(kMacBlock) syn_list_kernel(SynArgs a)
 {
     constexpr int W = Gran<VEC>::W;
-    constexpr int PD = PDX ? PDX : (VEC >= 32 ? KFEC_PD : 2 * KFEC_PD);
+    constexpr int PD = PDX ? PDX : (VEC >= 32 ? kPD : 2 * kPD);
     constexpr int TD = SynLayout<RT>::TD;
     __shared__ __attribute__((aligned(16))) uint32_t s_ct[kMacBlock / 64][RT * TD];
     const uint32_t cnt = *a.list_count;
@@ -1955,63 +1688,43 @@ __global__ void __launch_bounds__(kMacBlock) syn_list_kernel(SynArgs a)
                     (void *)(a.data + (uint64_t)g * a.K * a.pitch), (short)0, (int)(a.K * a.pitch), 0x00020000);
                 const __amdgpu_buffer_rsrc_t rp = __builtin_amdgcn_make_buffer_rsrc(
                     (void *)(a.parity + (uint64_t)g * a.R * a.pitch), (short)0, (int)(a.R * a.pitch), 0x00020000);
-                syn_loop<VEC, RT, PD, ROWS, (KFEC_SYN_PAIR & 2) != 0>(a, acc, rd, rp, off, off, used, p0, rec);
+                syn_loop<VEC, RT, PD, ROWS>(a, acc, rd, rp, off, off, used, p0, rec);
             }
             // the tables were written by lanes of this wave: LDS operations of one wave complete in order, the
             // fence keeps the compiler from moving the reads above the writes
             __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-            if (in) syn_final<VEC, RT, ROWS, KFEC_SYN_FINAL_ROWS != 0>(a, acc, ct, m, g, off, col);
+            if (in) syn_final<VEC, RT, ROWS, true>(a, acc, ct, m, g, off, col);
         });
         __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");  // the next task rewrites the tables
     }
 }
 
-#ifndef KFEC_SYN_WAVE_CT
-#define KFEC_SYN_WAVE_CT 1  // 0: one set of C tables per workgroup behind a workgroup barrier (A/B knob)
-#endif
 // groups one wave of 64 consecutive items can touch
 __host__ __device__ constexpr uint32_t syn_wave_groups(size_t cols) { return (uint32_t)(63 / (cols ? cols : 1) + 2); }
 
 template <int VEC, int RT, int PDX = 0>
-__global__ void __launch_bounds__(kMacBlock, KFEC_SYN_MINW) syn_kernel(SynArgs a)
+__global__ void __launch_bounds__(kMacBlock, kSynMinWaves) syn_kernel(SynArgs a)
 {
     constexpr int W = Gran<VEC>::W;
-    constexpr int PD = PDX ? PDX : (VEC >= 32 ? KFEC_PD : 2 * KFEC_PD);
+    constexpr int PD = PDX ? PDX : (VEC >= 32 ? kPD : 2 * kPD);
     constexpr int TD = SynLayout<RT>::TD;
-    extern __shared__ __attribute__((aligned(16))) uint32_t s_ct[];  // [wave][group slot][RT][TD] or [group slot][RT][TD]
+    extern __shared__ __attribute__((aligned(16))) uint32_t s_ct[];  // [wave][group slot][RT][TD]
     if (a.list_count && syn_listed(a, *a.list_count)) return;  // the listed kernel has it (whole workgroup)
     const uint32_t base = xcd_chunk(blockIdx.x) * kMacBlock;
     if (base >= a.total) return;  // padding chunk of the XCD-ordered grid (whole workgroup)
     const uint32_t cols = a.cols, K = a.K;
     const uint32_t gfirst = base / cols;
-#if KFEC_SYN_WAVE_CT
     // C tables of the groups this wave touches, built and read by this wave only: no workgroup barrier, so a
     // wave that finishes its shards does not wait for the slowest wave of the workgroup
     const uint32_t wbase = min(base + (threadIdx.x & ~63u), a.total - 1);
     const uint32_t wfirst = wbase / cols, wlast = min(wbase + 63, a.total - 1) / cols;
     uint32_t *ctw = s_ct + (threadIdx.x / 64) * syn_wave_groups(cols) * RT * TD;
     const uint32_t ne = (wlast - wfirst + 1) * RT * RT;
-#if KFEC_SYN_EARLY
     // the first 64 entries' coefficient bytes are loaded now, with the record header below, and expanded into
     // LDS after the shard loop: the shard loads wait for one dependent load (the header), not three
     const uint32_t e0 = threadIdx.x & 63u;
     const uint32_t e0g = min(e0, ne - 1) / (RT * RT);
     const uint32_t c_e0 = syn_coef<RT>(a.rec + (uint64_t)(wfirst + e0g) * a.rec_stride, min(e0, ne - 1) - e0g * (RT * RT));
-#else
-    for (uint32_t e = threadIdx.x & 63u; e < ne; e += 64) {
-        const uint32_t gs = e / (RT * RT);
-        syn_expand_one<RT>(a.rec + (uint64_t)(wfirst + gs) * a.rec_stride, e - gs * (RT * RT), ctw + gs * RT * TD);
-    }
-#endif
-#else
-    const uint32_t glast = min(base + kMacBlock - 1, a.total - 1) / cols;
-    const uint32_t ng = glast - gfirst + 1;
-    // C tables of the workgroup's groups
-    for (uint32_t e = threadIdx.x; e < ng * RT * RT; e += kMacBlock) {
-        const uint32_t gs = e / (RT * RT);
-        syn_expand_one<RT>(a.rec + (uint64_t)(gfirst + gs) * a.rec_stride, e - gs * (RT * RT), s_ct + gs * RT * TD);
-    }
-#endif
     const uint32_t item = base + threadIdx.x;
     const bool in = item < a.total;
     const uint32_t g = in ? item / cols : gfirst;
@@ -2043,22 +1756,15 @@ __global__ void __launch_bounds__(kMacBlock, KFEC_SYN_MINW) syn_kernel(SynArgs a
         syn_loop<VEC, RT, PD>(a, acc, rd, rp, gs * K * (uint32_t)a.pitch + off, gs * a.R * (uint32_t)a.pitch + off, used,
                               p0, rec);
     }
-#if KFEC_SYN_WAVE_CT
-#if KFEC_SYN_EARLY
     if (e0 < ne) syn_expand_put<RT>(c_e0, e0 - e0g * (RT * RT), ctw + e0g * RT * TD);
     for (uint32_t e = e0 + 64; e < ne; e += 64) {  // (more than 64 entries: pitch < 64 bytes per group)
         const uint32_t gs = e / (RT * RT);
         syn_expand_one<RT>(a.rec + (uint64_t)(wfirst + gs) * a.rec_stride, e - gs * (RT * RT), ctw + gs * RT * TD);
     }
-#endif
     // written by lanes of this wave: LDS operations of one wave complete in order; the fence keeps the
     // compiler from moving the reads above the writes
     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
     if (active) syn_final<VEC, RT>(a, acc, ctw + (g - wfirst) * RT * TD, m, g, off, col);
-#else
-    __syncthreads();  // C tables
-    if (active) syn_final<VEC, RT>(a, acc, s_ct + gs * RT * TD, m, g, off, col);
-#endif
 }
 
 // ---- ordered list of the groups with data to recover (out_idx[g * R] != 0xFF), for syn_kernel's listed
@@ -2159,12 +1865,12 @@ static int pick_vec_mac(size_t pitch, size_t B, std::initializer_list<const void
     return B >= 32 ? 32 : kLatencyVec;  // (B < 32: the dword shape, one granule per dword)
 }
 
-// output rows per tile: MT = R up to 4, else 8-row tiles.  Measured at 200:55: taller tiles on
-// narrower granules read each input byte fewer times but are no faster (VALU-bound there, and 32-B
+// output rows per tile of the encode: MT = R up to 4, else 8-row tiles.  Measured at 200:55: taller
+// tiles on narrower granules read each input byte fewer times but are no faster (VALU-bound there, and 32-B
 // granules amortise each table read over the most bytes).
 static int pick_mt(int R) { return R <= 4 ? std::max(R, 1) : 8; }
 
-// The encode's row tile for 32-byte granules.  R <= 8: one tile of R rows (R = 5..7 with the paired MAC, KFEC_ENC_MT_MID).
+// The encode's row tile for 32-byte granules.  R <= 8: one tile of R rows (R = 5..7 with the paired MAC, see mac_kernel).
 // R > 8: the height among 5..8 and 10 of least modelled VALU per (shard, dword) -- tiles x (4.5 per row for the paired
 // MAC + 5 for the selector extractions every tile repeats), ties to the taller tile.  All of them run at 3 or more
 // waves per SIMD (127-167 VGPRs) at about the same cost per row, so the rows a partial last tile wastes decide:
@@ -2174,16 +1880,14 @@ static int pick_mt(int R) { return R <= 4 ? std::max(R, 1) : 8; }
 // profiles/r06_mt_model_ab.txt)
 static int pick_mt_enc(int R)
 {
-    if (R <= 8) return KFEC_ENC_MT_MID != 0 && R >= 5 ? R : pick_mt(R);
+    if (R <= 8) return std::max(R, 1);
     int best = 8, best_cost = 1 << 30;
     for (int mt : {10, 8, 7, 6, 5}) {
-        if (KFEC_ENC_MT_MID == 0 && mt < 8) continue;
         const int cost = (R + mt - 1) / mt * (9 * mt + 10);
         if (cost < best_cost) best = mt, best_cost = cost;
     }
     return best;
 }
-
 
 #if KFEC_MAC_XORONLY || KFEC_SYN_XORONLY
 // The arithmetic-free ceiling build only (tools/libkfec_arithfree.so): KFEC_AF_WAVES = n caps a launch at n 256-lane
@@ -2205,105 +1909,57 @@ static size_t af_lds(size_t lds) { return lds; }
 template <int VEC, int MT, bool DEC, int PDX = 0>
 static int run_mac(MacArgs a, hipStream_t s)
 {
-    using L = MacLayout<MT>;
-    const size_t lds = af_lds((DEC && dec_ttab(MT)) ? kTBytes + kDecGfBytes + (size_t)a.gmax * a.JC * kDecEntry
-                                                                : (size_t)a.gmax * a.JC * L::ENTRY);
+    const size_t lds = af_lds(DEC ? kTBytes + kDecGfBytes + (size_t)a.gmax * a.JC * kDecEntry
+                                  : (size_t)a.gmax * a.JC * MacLayout<MT>::ENTRY);
     const uint32_t chunks = (a.total + kMacBlock - 1) / kMacBlock;
     const uint32_t nb = a.tiles > 1 ? xcd_tile_chunks(chunks) * a.tiles : xcd_grid(chunks);
     hipLaunchKernelGGL((mac_kernel<VEC, MT, DEC, PDX>), dim3(std::max(1u, nb)), dim3(kMacBlock), lds, s, a);
     return hipGetLastError() == hipSuccess ? 0 : -3;
 }
 
+// Only the (granule, row tile) pairs launch_encode / launch_decode ask for are instantiated.
 template <bool DEC>
 static int dispatch_mac(int vec, int mt, MacArgs a, hipStream_t s)
 {
-#if KFEC_SYN_MAX_R > 0
-    if constexpr (DEC) {  // coefficient-form decode: R > 8, 8-row tiles only
-        (void)mt;
+    if constexpr (DEC) {  // coefficient form: 8-row tiles, or launch_decode's 4..7-row tiles of 32-byte granules
         if (vec == kLatencyVec) return run_mac<4, 8, true, 16>(a, s);
-        if constexpr (KFEC_DEC_MT_SMALL != 0)
-            if (vec == 32 && mt == 4) return run_mac<32, 4, true>(a, s);
-        if constexpr (KFEC_DEC_MT_MID != 0) {
-            if (vec == 32 && mt == 5) return run_mac<32, 5, true>(a, s);
-            if (vec == 32 && mt == 6) return run_mac<32, 6, true>(a, s);
-            if (vec == 32 && mt == 7) return run_mac<32, 7, true>(a, s);
-        }
-        if (vec == 32) return run_mac<32, 8, true>(a, s);
-        return run_mac<1, 8, true>(a, s);
-    }
-#endif
-    if (vec == kLatencyVec) {  // the latency shape: dword granules, 16 shards in flight per lane
+        if (vec != 32) return run_mac<1, 8, true>(a, s);
         switch (mt) {
-        case 1: return run_mac<4, 1, DEC, 16>(a, s);
-        case 2: return run_mac<4, 2, DEC, 16>(a, s);
-        case 3: return run_mac<4, 3, DEC, 16>(a, s);
-        case 4: return run_mac<4, 4, DEC, 16>(a, s);
-        default: return run_mac<4, 8, DEC, 16>(a, s);
+        case 4: return run_mac<32, 4, true>(a, s);
+        case 5: return run_mac<32, 5, true>(a, s);
+        case 6: return run_mac<32, 6, true>(a, s);
+        case 7: return run_mac<32, 7, true>(a, s);
+        default: return run_mac<32, 8, true>(a, s);
         }
-    }
-    if (vec == 32) {
-        if constexpr (!DEC) {
-            if (mt == 10) return run_mac<32, 10, false>(a, s);
-            if constexpr (KFEC_ENC_MT_MID != 0) {
-                if (mt == 5) return run_mac<32, 5, false>(a, s);
-                if (mt == 6) return run_mac<32, 6, false>(a, s);
-                if (mt == 7) return run_mac<32, 7, false>(a, s);
-            }
-        }
+    } else if (vec == kLatencyVec) {  // the latency shape: dword granules, 16 shards in flight per lane
         switch (mt) {
-        case 1: return run_mac<32, 1, DEC>(a, s);
-        case 2: return run_mac<32, 2, DEC>(a, s);
-        case 3: return run_mac<32, 3, DEC>(a, s);
-        case 4: return run_mac<32, 4, DEC>(a, s);
-        default: return run_mac<32, 8, DEC>(a, s);
+        case 1: return run_mac<4, 1, false, 16>(a, s);
+        case 2: return run_mac<4, 2, false, 16>(a, s);
+        case 3: return run_mac<4, 3, false, 16>(a, s);
+        case 4: return run_mac<4, 4, false, 16>(a, s);
+        default: return run_mac<4, 8, false, 16>(a, s);
+        }
+    } else if (vec == 32) {  // pick_mt_enc
+        switch (mt) {
+        case 1: return run_mac<32, 1, false>(a, s);
+        case 2: return run_mac<32, 2, false>(a, s);
+        case 3: return run_mac<32, 3, false>(a, s);
+        case 4: return run_mac<32, 4, false>(a, s);
+        case 5: return run_mac<32, 5, false>(a, s);
+        case 6: return run_mac<32, 6, false>(a, s);
+        case 7: return run_mac<32, 7, false>(a, s);
+        case 10: return run_mac<32, 10, false>(a, s);
+        default: return run_mac<32, 8, false>(a, s);
+        }
+    } else {
+        switch (mt) {
+        case 1: return run_mac<1, 1, false>(a, s);
+        case 2: return run_mac<1, 2, false>(a, s);
+        case 3: return run_mac<1, 3, false>(a, s);
+        case 4: return run_mac<1, 4, false>(a, s);
+        default: return run_mac<1, 8, false>(a, s);
         }
     }
-    switch (mt) {
-    case 1: return run_mac<1, 1, DEC>(a, s);
-    case 2: return run_mac<1, 2, DEC>(a, s);
-    case 3: return run_mac<1, 3, DEC>(a, s);
-    case 4: return run_mac<1, 4, DEC>(a, s);
-    default: return run_mac<1, 8, DEC>(a, s);
-    }
-}
-
-static int entry_bytes(int mt)
-{
-    switch (mt) {
-    case 1: return MacLayout<1>::ENTRY;
-    case 2: return MacLayout<2>::ENTRY;
-    case 3: return MacLayout<3>::ENTRY;
-    case 4: return MacLayout<4>::ENTRY;
-    case 5: return MacLayout<5>::ENTRY;
-    case 6: return MacLayout<6>::ENTRY;
-    case 7: return MacLayout<7>::ENTRY;
-    case 10: return MacLayout<10>::ENTRY;
-    default: return MacLayout<8>::ENTRY;
-    }
-}
-
-
-static size_t syn_td(int rt)
-{
-    switch (rt) {
-    case 1: return SynLayout<1>::TD;
-    case 2: return SynLayout<2>::TD;
-    case 3: return SynLayout<3>::TD;
-    case 4: return SynLayout<4>::TD;
-    case 5: return SynLayout<5>::TD;
-    case 6: return SynLayout<6>::TD;
-    case 7: return SynLayout<7>::TD;
-    default: return SynLayout<8>::TD;
-    }
-}
-
-#ifndef KFEC_SYN_WAVES
-#define KFEC_SYN_WAVES 0  // syn_kernel capped at this many workgroups (= waves) per SIMD by padding its LDS (0: no cap)
-#endif
-static size_t syn_cap(size_t lds)
-{
-    if (KFEC_SYN_WAVES < 2) return lds;
-    return std::max(lds, std::min<size_t>((size_t)160 * 1024 / (KFEC_SYN_WAVES + 1) + 64, 64 * 1024));
 }
 
 template <int VEC, int RT, int PDX = 0>
@@ -2311,7 +1967,7 @@ static int run_syn(SynArgs a, size_t lds, int cus, hipStream_t s)
 {
     const uint32_t nb = xcd_grid((a.total + kMacBlock - 1) / kMacBlock);
     if (!a.no_dense)
-        hipLaunchKernelGGL((syn_kernel<VEC, RT, PDX>), dim3(std::max(1u, nb)), dim3(kMacBlock), af_lds(syn_cap(lds)), s, a);
+        hipLaunchKernelGGL((syn_kernel<VEC, RT, PDX>), dim3(std::max(1u, nb)), dim3(kMacBlock), af_lds(lds), s, a);
     if (!a.list_count) return hipGetLastError() == hipSuccess ? 0 : -3;  // dense only
     // the listed shape: persistent, ~8 workgroups per CU, at most one wave per (group, 64 columns) task
     const uint64_t tasks = (uint64_t)a.G * (a.cols_pad / 64);
@@ -2320,28 +1976,31 @@ static int run_syn(SynArgs a, size_t lds, int cus, hipStream_t s)
     return hipGetLastError() == hipSuccess ? 0 : -3;
 }
 
+template <int VEC, int PDX>
+static int dispatch_syn_rt(int rt, SynArgs a, size_t lds, int cus, hipStream_t s)
+{
+    switch (rt) {
+    case 1: return run_syn<VEC, 1, PDX>(a, lds, cus, s);
+    case 2: return run_syn<VEC, 2, PDX>(a, lds, cus, s);
+    case 3: return run_syn<VEC, 3, PDX>(a, lds, cus, s);
+    case 4: return run_syn<VEC, 4, PDX>(a, lds, cus, s);
+    case 5: return run_syn<VEC, 5, PDX>(a, lds, cus, s);
+    case 6: return run_syn<VEC, 6, PDX>(a, lds, cus, s);
+    case 7: return run_syn<VEC, 7, PDX>(a, lds, cus, s);
+    default: return run_syn<VEC, 8, PDX>(a, lds, cus, s);
+    }
+}
+
+// Every (granule, RT) pair has both shapes, and each is reachable:
+//  * syn_kernel<32, 4..8> (dense, 32-byte granules, hybrid R): the hybrid decode launches only the listed kernel for
+//    these R, but launch_decode leaves the hybrid path when G * cols > kMaxItemsPerLaunch, and the plain syndrome
+//    path then launches the dense kernel per group range;
+//  * syn_list_kernel<4, RT, 16> (listed, dword granules): pick_vec_mac takes dword granules for every B < 32 whatever
+//    G is, and such a batch of more than kLatencyGroups groups builds the list and launches the listed kernel.
 static int dispatch_syn(int vec, int rt, SynArgs a, size_t lds, int cus, hipStream_t s)
 {
-#define KFEC_RT_CASES(V, P)                                                          \
-    do {                                                                             \
-        switch (rt) {                                                                \
-        case 1: return run_syn<V, 1, P>(a, lds, cus, s);                             \
-        case 2: return run_syn<V, 2, P>(a, lds, cus, s);                             \
-        case 3: return run_syn<V, 3, P>(a, lds, cus, s);                             \
-        case 4: return run_syn<V, 4, P>(a, lds, cus, s);                             \
-        case 5: if constexpr (KFEC_SYN_RT_MID != 0) return run_syn<V, 5, P>(a, lds, cus, s); break; \
-        case 6: if constexpr (KFEC_SYN_RT_MID != 0) return run_syn<V, 6, P>(a, lds, cus, s); break; \
-        case 7: if constexpr (KFEC_SYN_RT_MID != 0) return run_syn<V, 7, P>(a, lds, cus, s); break; \
-        default: break;                                                              \
-        }                                                                            \
-        return run_syn<V, 8, P>(a, lds, cus, s);                                     \
-    } while (0)
-    if (vec == kLatencyVec) KFEC_RT_CASES(4, 16);
-#if KFEC_SYN_SMALLK_PD > 0
-    if (a.K <= 12) KFEC_RT_CASES(32, KFEC_SYN_SMALLK_PD);
-#endif
-    KFEC_RT_CASES(32, 0);
-#undef KFEC_RT_CASES
+    if (vec == kLatencyVec) return dispatch_syn_rt<4, 16>(rt, a, lds, cus, s);
+    return dispatch_syn_rt<32, 0>(rt, a, lds, cus, s);
 }
 
 static constexpr size_t kLdsBudget = 32 * 1024;
@@ -2374,7 +2033,7 @@ int launch_encode(const DeviceInfo &di, const uint8_t *d_enc, int K, int N, size
     const int vb = vec >= 4 ? vec : 4;
     const size_t cols = (B + vb - 1) / vb;
     const int tiles = (R + mt - 1) / mt;
-    const size_t ent = entry_bytes(mt);
+    const size_t ent = 16 + 4 * table_dwords(mt);  // MacLayout<mt>::ENTRY
     const uint32_t JC = (uint32_t)std::max<size_t>(1, std::min<size_t>(K, kLdsBudget / ent));
     return for_group_ranges(G, cols, tiles, [&](size_t g0, size_t gn) {
         MacArgs a{};
@@ -2407,7 +2066,7 @@ int launch_decode_prep(const DeviceInfo &di, const uint8_t *d_enc, int K, int N,
     if (G == 0) return 0;
     uint8_t *rec = static_cast<uint8_t *>(d_workspace);
     factored = factored && !syn && std::min(K, R) > 8;  // (only decode_prep_lagrange writes the factored form)
-    const size_t rs = syn ? syn_record_stride(K, R) : factored ? fac_record_stride(K, R) : record_stride(K, R);
+    const size_t rs = syn ? syn_record_stride(R) : factored ? fac_record_stride(K, R) : record_stride(K, R);
     PrepArgs p{};
     p.present = d_present;
     p.enc = d_enc;
@@ -2424,34 +2083,44 @@ int launch_decode_prep(const DeviceInfo &di, const uint8_t *d_enc, int K, int N,
     p.cols_pad = cols_pad;
     const int mmax = std::min(K, R);
     if (mmax <= 8) {
-        const size_t lds = 768 + (size_t)R * K;
         // one thread per group: the per-group work is a chain of dependent LDS lookups, so latency is hidden
         // by having many groups in flight, not by looping
         const uint32_t blocks = (uint32_t)std::max<size_t>(1, std::min<size_t>((G + kBlock - 1) / kBlock,
                                                                                 (size_t)std::max(di.cus, 1) * 64));
-        const size_t lds4 = 768 + (size_t)R * (((size_t)K + 3) & ~size_t(3));
-        if (syn && KFEC_PREP_SYN_T) {
-            if (mmax == 1) hipLaunchKernelGGL((decode_prep_perm<1, true>), dim3(blocks), dim3(kBlock), lds4, s, p);
-            else if (mmax == 2) hipLaunchKernelGGL((decode_prep_perm<2, true>), dim3(blocks), dim3(kBlock), lds4, s, p);
-            else if (mmax == 3) hipLaunchKernelGGL((decode_prep_perm<3, true>), dim3(blocks), dim3(kBlock), lds4, s, p);
-            else if (mmax == 4) hipLaunchKernelGGL((decode_prep_perm<4, true>), dim3(blocks), dim3(kBlock), lds4, s, p);
-            else hipLaunchKernelGGL((decode_prep_small<8>), dim3(blocks), dim3(kBlock), lds, s, p);
+        const size_t lds = 768 + (size_t)R * K;                                  // decode_prep_small: parity rows, R x K
+        const size_t lds4 = 768 + (size_t)R * (((size_t)K + 3) & ~size_t(3));  // decode_prep_perm: R x K4
+        auto launch = [&](void (*kernel)(PrepArgs), size_t bytes) {
+            hipLaunchKernelGGL(kernel, dim3(blocks), dim3(kBlock), bytes, s, p);
+        };
+        // (the syndrome-record form of decode_prep_perm is its own instantiation, see there)
+        switch (mmax) {
+        case 1: launch(syn ? decode_prep_perm<1, true> : decode_prep_perm<1>, lds4); break;
+        case 2: launch(syn ? decode_prep_perm<2, true> : decode_prep_perm<2>, lds4); break;
+        case 3: launch(syn ? decode_prep_perm<3, true> : decode_prep_perm<3>, lds4); break;
+        case 4: launch(syn ? decode_prep_perm<4, true> : decode_prep_perm<4>, lds4); break;
+        default: launch(decode_prep_small<8>, lds); break;
         }
-        else if (mmax == 1) hipLaunchKernelGGL((decode_prep_perm<1>), dim3(blocks), dim3(kBlock), lds4, s, p);
-        else if (mmax == 2) hipLaunchKernelGGL((decode_prep_perm<2>), dim3(blocks), dim3(kBlock), lds4, s, p);
-        else if (mmax == 3) hipLaunchKernelGGL((decode_prep_perm<3>), dim3(blocks), dim3(kBlock), lds4, s, p);
-        else if (mmax == 4) hipLaunchKernelGGL((decode_prep_perm<4>), dim3(blocks), dim3(kBlock), lds4, s, p);
-        else hipLaunchKernelGGL((decode_prep_small<8>), dim3(blocks), dim3(kBlock), lds, s, p);
     } else {
-        constexpr int kTeam = KFEC_PREP_WAVE ? 64 : kPrepThreads;
-        const void *fn = reinterpret_cast<const void *>(&decode_prep_lagrange<kTeam>);
+        const void *fn = reinterpret_cast<const void *>(&decode_prep_lagrange);
         int occ = 0;
         if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, fn, kPrepThreads, 0) != hipSuccess || occ <= 0) occ = 1;
-        const size_t teams = kPrepThreads / kTeam;
+        const size_t teams = kPrepThreads / kPrepTeam;
         const uint32_t blocks =
             (uint32_t)std::max<size_t>(1, std::min<size_t>((G + teams - 1) / teams, (size_t)std::max(di.cus, 1) * occ));
-        hipLaunchKernelGGL((decode_prep_lagrange<kTeam>), dim3(blocks), dim3(kPrepThreads), 0, s, p);
+        hipLaunchKernelGGL(decode_prep_lagrange, dim3(blocks), dim3(kPrepThreads), 0, s, p);
     }
+    return hipGetLastError() == hipSuccess ? 0 : -3;
+}
+
+// the ordered list of the G groups at out_idx with data to recover, and its length, on the device
+static int build_active_list(size_t G, int R, const uint8_t *out_idx, uint32_t *count, uint32_t *chunk_cnt, uint32_t *list,
+                             hipStream_t s)
+{
+    const uint32_t nch = (uint32_t)((G + kActChunk - 1) / kActChunk);
+    hipLaunchKernelGGL(active_count_kernel, dim3(nch), dim3(kBlock), 0, s, (uint64_t)G, (uint32_t)R, out_idx, chunk_cnt);
+    hipLaunchKernelGGL(active_scan_kernel, dim3(1), dim3(kBlock), 0, s, nch, chunk_cnt, count);
+    hipLaunchKernelGGL(active_scatter_kernel, dim3(nch), dim3(kBlock), 0, s, (uint64_t)G, (uint32_t)R, out_idx,
+                       (const uint32_t *)chunk_cnt, list);
     return hipGetLastError() == hipSuccess ? 0 : -3;
 }
 
@@ -2462,156 +2131,113 @@ int launch_decode(const DeviceInfo &di, const uint8_t *d_enc, int K, int N, size
     const int R = N - K;
     if (G == 0) return 0;
     uint8_t *rec = static_cast<uint8_t *>(d_workspace);
-    const size_t rs = record_stride(K, R);
     int vec = pick_vec_mac(pitch, B, {d_data, d_parity, d_out});
     if (G <= kLatencyGroups && vec >= 4) vec = kLatencyVec;
     const int vb = vec >= 4 ? vec : 4;
     const size_t cols = (B + vb - 1) / vb;
-    // syndrome form for R <= 8 unless its per-workgroup C tables outgrow LDS (tiny B: hundreds of groups
-    // per workgroup)
+    const size_t cols_pad = (cols + 63) / 64 * 64;
+    // syndrome form for R <= 8 unless its per-wave C tables outgrow LDS (tiny B: hundreds of groups per workgroup)
     const int rt = syn_rt(R);
     const size_t gmax_syn = std::min<size_t>(G, (kMacBlock - 1) / std::max<size_t>(cols, 1) + 2);
-    const size_t lds_syn = (KFEC_SYN_WAVE_CT ? (size_t)(kMacBlock / 64) * syn_wave_groups(cols) : gmax_syn) *
-                           (size_t)rt * syn_td(rt) * 4;
+    const size_t lds_syn = (size_t)(kMacBlock / 64) * syn_wave_groups(cols) * (size_t)rt * table_dwords(rt) * 4;
     // (syndrome form: whole-dword granules, and each workgroup's groups must fit one buffer resource)
-    const bool syn = R > 0 && R <= KFEC_SYN_MAX_R && lds_syn <= kSynLdsMax && vec != 1 &&
+    const bool syn = R > 0 && R <= 8 && lds_syn <= kSynLdsMax && vec != 1 &&
                      gmax_syn * (size_t)K * pitch < (size_t(1) << 31) && gmax_syn * (size_t)R * pitch < (size_t(1) << 31) &&
                      G * (size_t)R < (size_t(1) << 32);
     // (the mac_kernel decode rebuilds the coefficients of factored records; the prep writes them for K, R > 8)
-    const bool factored = !syn && KFEC_DEC_FACTORED && KFEC_DEC_TTAB && std::min(K, R) > 8;
-    // hybrid (decode_hybrid_r): the listed syndrome kernel for sparse loss, the coefficient-form MAC (3 waves per
-    // SIMD against the RT >= 6 syndrome kernel's 2) for dense loss, chosen on the device by the same rule
-    const bool hybrid = syn && decode_hybrid_r(R) && vec == 32 && G > kLatencyGroups && B > 0 &&
-                        G * cols <= kMaxItemsPerLaunch && KFEC_DEC_TTAB;
-    if (hybrid) {
-        // syndrome records and the list first; the coefficient records only when the dense shape will run (the
-        // prep exits at once otherwise)
-        uint8_t *rec_syn = rec + decode_hybrid_syn_offset(G, K, R);
-        if (launch_decode_prep(di, d_enc, K, N, G, d_present, d_out_idx, d_status, rec_syn, s, true, false)) return -3;
-        uint32_t *count = reinterpret_cast<uint32_t *>(rec + decode_list_offset(G, K, R));
-        uint32_t *chunk_cnt = count + 64;
-        uint32_t *list = chunk_cnt + decode_list_chunks(G);
-        const size_t cols_pad = (cols + 63) / 64 * 64;
-        const uint32_t nch = (uint32_t)((G + kActChunk - 1) / kActChunk);
-        hipLaunchKernelGGL(active_count_kernel, dim3(nch), dim3(kBlock), 0, s, (uint64_t)G, (uint32_t)R, d_out_idx, chunk_cnt);
-        hipLaunchKernelGGL(active_scan_kernel, dim3(1), dim3(kBlock), 0, s, nch, chunk_cnt, count);
-        hipLaunchKernelGGL(active_scatter_kernel, dim3(nch), dim3(kBlock), 0, s, (uint64_t)G, (uint32_t)R, d_out_idx,
-                           (const uint32_t *)chunk_cnt, list);
-        if (hipGetLastError() != hipSuccess) return -3;
-        if (launch_decode_prep(di, d_enc, K, N, G, d_present, d_out_idx, d_status, d_workspace, s, false, false, count,
-                               (uint32_t)cols, (uint32_t)cols_pad))
-            return -3;
-        SynArgs sa{};
-        sa.data = static_cast<const uint8_t *>(d_data);
-        sa.parity = static_cast<const uint8_t *>(d_parity);
-        sa.out = static_cast<uint8_t *>(d_out);
-        sa.rec = rec_syn;
-        sa.etab = reinterpret_cast<const uint32_t *>(d_enc + enc_tab_offset(K, N));
-        sa.list = list;
-        sa.list_count = count;
-        sa.etab_rows = (uint32_t)enc_tab_rows(R);
-        sa.pitch = pitch;
-        sa.total = (uint32_t)(G * cols);
-        sa.cols = (uint32_t)cols;
-        sa.cols_pad = (uint32_t)cols_pad;
-        sa.G = (uint32_t)G;
-        sa.K = K; sa.R = R; sa.B = (uint32_t)B;
-        sa.rec_stride = (uint32_t)syn_record_stride(K, R);
-        sa.no_dense = 1;
-        if (dispatch_syn(vec, rt, sa, lds_syn, di.cus, s)) return -3;
-        const uint32_t gmax = (uint32_t)std::min<size_t>(G, (kMacBlock - 1) / cols + 2);
-        MacArgs a{};
-        a.data = static_cast<const uint8_t *>(d_data);
-        a.parity = static_cast<const uint8_t *>(d_parity);
-        a.out = static_cast<uint8_t *>(d_out);
-        a.enc = d_enc;
-        a.rec = rec;
+    const bool factored = !syn && std::min(K, R) > 8;
+    // the active-group list after the records (kfec_internal.hpp decode_list_offset)
+    uint32_t *count = reinterpret_cast<uint32_t *>(rec + decode_list_offset(G, K, R));
+    uint32_t *chunk_cnt = count + 64;
+    uint32_t *list = chunk_cnt + decode_list_chunks(G);
+
+    // groups [g0, g0 + gn) for the syndrome kernels; list_count = nullptr: dense only (no listed launch)
+    auto syn_args = [&](size_t g0, size_t gn, const uint8_t *rec_syn, const uint32_t *list_count) {
+        SynArgs a{};
+        a.data = static_cast<const uint8_t *>(d_data) + g0 * K * pitch;
+        a.parity = static_cast<const uint8_t *>(d_parity) + g0 * R * pitch;
+        a.out = static_cast<uint8_t *>(d_out) + g0 * R * pitch;
+        a.rec_stride = (uint32_t)syn_record_stride(R);
+        a.rec = rec_syn + g0 * a.rec_stride;
+        a.etab = reinterpret_cast<const uint32_t *>(d_enc + enc_tab_offset(K, N));
+        a.list = list;
+        a.list_count = list_count;
+        a.etab_rows = (uint32_t)enc_tab_rows(R);
         a.pitch = pitch;
-        a.total = (uint32_t)(G * cols);
+        a.total = (uint32_t)(gn * cols);
         a.cols = (uint32_t)cols;
-        a.G = (uint32_t)G;
-        a.K = K; a.R = R; a.B = (uint32_t)B;
-        a.rec_stride = (uint32_t)rs;
-        a.factored = 0;
-        a.JC = (uint32_t)std::max<size_t>(1, std::min<size_t>(K, kDecLdsBudget / (kDecEntry * gmax)));
-        a.gmax = gmax;
-        a.tiles = 1;
-        a.list_count = count;
         a.cols_pad = (uint32_t)cols_pad;
-        return dispatch_mac<true>(vec, (KFEC_DEC_MT_MID && R >= 5 && R < 8) || (KFEC_DEC_MT_SMALL && R == 4) ? R : 8, a, s);
-    }
-    if (launch_decode_prep(di, d_enc, K, N, G, d_present, d_out_idx, d_status, d_workspace, s, syn, factored)) return -3;
-    if (R == 0 || B == 0) return 0;
-    if (syn) {
-        const size_t rs_syn = syn_record_stride(K, R);  // (the prep wrote syndrome records)
-        uint32_t *count = reinterpret_cast<uint32_t *>(rec + decode_list_offset(G, K, R));
-        uint32_t *chunk_cnt = count + 64;
-        uint32_t *list = chunk_cnt + decode_list_chunks(G);
-        const size_t cols_pad = (cols + 63) / 64 * 64;
-        const size_t lds = lds_syn;
-        return for_group_ranges(G, cols, 1, [&](size_t g0, size_t gn) {
-            // the ordered list of this launch's groups with data to recover, and its length, on the device
-            // (not for the latency shape's few groups: there the dense kernel alone runs, two launches fewer
-            // per decode call plus the listed kernel's)
-            const bool small = gn <= kLatencyGroups;
-            const uint32_t nch = (uint32_t)((gn + kActChunk - 1) / kActChunk);
-            const uint8_t *oi = d_out_idx + g0 * R;
-            if (!small) {
-                hipLaunchKernelGGL(active_count_kernel, dim3(nch), dim3(kBlock), 0, s, (uint64_t)gn, (uint32_t)R, oi, chunk_cnt);
-                hipLaunchKernelGGL(active_scan_kernel, dim3(1), dim3(kBlock), 0, s, nch, chunk_cnt, count);
-                hipLaunchKernelGGL(active_scatter_kernel, dim3(nch), dim3(kBlock), 0, s, (uint64_t)gn, (uint32_t)R, oi,
-                                   (const uint32_t *)chunk_cnt, list);
-                if (hipGetLastError() != hipSuccess) return -3;
-            }
-            SynArgs a{};
-            a.data = static_cast<const uint8_t *>(d_data) + g0 * K * pitch;
-            a.parity = static_cast<const uint8_t *>(d_parity) + g0 * R * pitch;
-            a.out = static_cast<uint8_t *>(d_out) + g0 * R * pitch;
-            a.rec = rec + g0 * rs_syn;
-            a.etab = reinterpret_cast<const uint32_t *>(d_enc + enc_tab_offset(K, N));
-            a.list = list;
-            a.list_count = small ? nullptr : count;  // nullptr: dense only (syn_kernel runs, no listed launch)
-            a.etab_rows = (uint32_t)enc_tab_rows(R);
-            a.pitch = pitch;
-            a.total = (uint32_t)(gn * cols);
-            a.cols = (uint32_t)cols;
-            a.cols_pad = (uint32_t)cols_pad;
-            a.G = (uint32_t)gn;
-            a.K = K; a.R = R; a.B = (uint32_t)B;
-            a.rec_stride = (uint32_t)rs_syn;
-            return dispatch_syn(vec, rt, a, lds, di.cus, s);
-        });
-    }
-#if KFEC_SYN_MAX_R > 0
-    // coefficient form: R > 8 (or tiny shards), 8-row tiles; KFEC_DEC_MT4_WIDE: 4-row tiles where they compute fewer
-    // rows (the factored records' scalar loads need row0 % 4 == 0)
-    const int mt = (KFEC_DEC_MT4_WIDE && KFEC_DEC_MT_SMALL && vec == 32 && (R + 3) / 4 * 4 < (R + 7) / 8 * 8) ? 4 : 8;
-#else
-    const int mt = pick_mt(R);  // A/B build: coefficient form for every R
-#endif
-    const int tiles = (R + mt - 1) / mt;
-    const size_t ent = entry_bytes(mt);
-    return for_group_ranges(G, cols, tiles, [&](size_t g0, size_t gn) {
+        a.G = (uint32_t)gn;
+        a.K = K; a.R = R; a.B = (uint32_t)B;
+        return a;
+    };
+    // groups [g0, g0 + gn) for the coefficient-form MAC with `tiles` row tiles over records of the given form
+    auto mac_args = [&](size_t g0, size_t gn, int tiles, bool fac) {
         const uint32_t gmax = (uint32_t)std::min<size_t>(gn, (kMacBlock - 1) / cols + 2);
-        const uint32_t JC = dec_ttab(mt) ? (uint32_t)std::max<size_t>(1, std::min<size_t>(K, kDecLdsBudget / (kDecEntry * gmax)))
-                                          : (uint32_t)std::max<size_t>(1, std::min<size_t>(K, kLdsBudget / (ent * gmax)));
         MacArgs a{};
         a.data = static_cast<const uint8_t *>(d_data) + g0 * K * pitch;
         a.parity = static_cast<const uint8_t *>(d_parity) + g0 * R * pitch;
         a.out = static_cast<uint8_t *>(d_out) + g0 * R * pitch;
         a.enc = d_enc;
-        a.rec = rec + g0 * rs;
+        a.rec_stride = (uint32_t)(fac ? fac_record_stride(K, R) : record_stride(K, R));
+        a.rec = rec + g0 * a.rec_stride;
         a.pitch = pitch;
         a.total = (uint32_t)(gn * cols);
         a.cols = (uint32_t)cols;
         a.G = (uint32_t)gn;
         a.K = K; a.R = R; a.B = (uint32_t)B;
-        a.rec_stride = (uint32_t)(factored ? fac_record_stride(K, R) : rs);
-        a.factored = factored ? 1u : 0u;
-        a.JC = JC;
+        a.factored = fac ? 1u : 0u;
+        a.JC = (uint32_t)std::max<size_t>(1, std::min<size_t>(K, kDecLdsBudget / (kDecEntry * gmax)));
         a.gmax = gmax;
         a.tiles = (uint32_t)tiles;
-        return dispatch_mac<true>(vec, mt, a, s);
+        return a;
+    };
+
+    // hybrid (decode_hybrid_r): the listed syndrome kernel for sparse loss, the coefficient-form MAC (3 waves per
+    // SIMD against the RT >= 6 syndrome kernel's 2) for dense loss, chosen on the device by the same rule
+    const bool hybrid = syn && decode_hybrid_r(R) && vec == 32 && G > kLatencyGroups && B > 0 &&
+                        G * cols <= kMaxItemsPerLaunch;
+    if (hybrid) {
+        // syndrome records and the list first; the coefficient records only when the dense shape will run (the
+        // prep exits at once otherwise)
+        uint8_t *rec_syn = rec + decode_hybrid_syn_offset(G, K, R);
+        if (launch_decode_prep(di, d_enc, K, N, G, d_present, d_out_idx, d_status, rec_syn, s, true, false)) return -3;
+        if (build_active_list(G, R, d_out_idx, count, chunk_cnt, list, s)) return -3;
+        if (launch_decode_prep(di, d_enc, K, N, G, d_present, d_out_idx, d_status, d_workspace, s, false, false, count,
+                               (uint32_t)cols, (uint32_t)cols_pad))
+            return -3;
+        SynArgs sa = syn_args(0, G, rec_syn, count);
+        sa.no_dense = 1;
+        if (dispatch_syn(vec, rt, sa, lds_syn, di.cus, s)) return -3;
+        MacArgs a = mac_args(0, G, 1, false);
+        a.list_count = count;
+        a.cols_pad = (uint32_t)cols_pad;
+        // one tile of R rows for R = 4..7 (129-149 VGPRs at 5..7) instead of an 8-row tile.  R = 5..7, with the hybrid
+        // from R = 5: dense 20:6 11.05 -> 9.87 ms, 10:6 random 5.99 -> 5.00, 16:7 9.63 -> 9.19, 20:5 9.06 -> 8.88,
+        // sparse unchanged (profiles/r06_dec_mt_mid_ab.txt).  R = 4: dense 8:4 decode 3.97 -> 3.72 ms; for R = 3 it
+        // was slower than the syndrome kernel (20:3 6.2-6.6 -> 6.7, 10:3 random 3.11 -> 3.28), so R = 3 stays
+        // syndrome-only (profiles/r06_dec_mt_small_ab.txt)
+        return dispatch_mac<true>(vec, R, a, s);
+    }
+    if (launch_decode_prep(di, d_enc, K, N, G, d_present, d_out_idx, d_status, d_workspace, s, syn, factored)) return -3;
+    if (R == 0 || B == 0) return 0;
+    if (syn) {
+        return for_group_ranges(G, cols, 1, [&](size_t g0, size_t gn) {
+            // the list of this launch's groups (not for the latency shape's few groups: there the dense kernel alone
+            // runs, two launches fewer per decode call plus the listed kernel's)
+            const bool small = gn <= kLatencyGroups;
+            if (!small && build_active_list(gn, R, d_out_idx + g0 * R, count, chunk_cnt, list, s)) return -3;
+            return dispatch_syn(vec, rt, syn_args(g0, gn, rec, small ? nullptr : count), lds_syn, di.cus, s);
+        });
+    }
+    // coefficient form: R > 8 (or tiny or unaligned shards), 8-row tiles; 4-row tiles of 32-byte granules where they
+    // compute fewer rows (the factored records' scalar loads need row0 % 4 == 0): 40:20 13.40 -> 12.62 ms, 30:20 random
+    // 6.97 -> 6.38, 30:12 14.57 -> 12.72, 40:20 at 1% loss 4.58 -> 3.23; 200:55 keeps 8-row tiles
+    // (profiles/r06_dec_mt4_ab.txt)
+    const int mt = (vec == 32 && (R + 3) / 4 * 4 < (R + 7) / 8 * 8) ? 4 : 8;
+    const int tiles = (R + mt - 1) / mt;
+    return for_group_ranges(G, cols, tiles, [&](size_t g0, size_t gn) {
+        return dispatch_mac<true>(vec, mt, mac_args(g0, gn, tiles, factored), s);
     });
 }
 

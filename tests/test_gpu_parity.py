@@ -208,7 +208,7 @@ CASES = [
     (6, 9, 2048, 2048, 5, 3, "B = 2048"),
     (6, 9, 2049, 2064, 5, 3, "B = 2049, pitch > B"),
     (3, 10, 100, 100, 50, None, "K < R: syndrome form RT=8 with prep MAXM=3"),
-    (5, 11, 1440, 1440, 40, None, "R=6 -> syndrome RT=6 (K < R), random erasures"),
+    (5, 11, 1440, 1440, 40, None, "R=6, K < R: hybrid decode, random (dense) erasures -> coefficient-form MAC MT=6"),
     (100, 104, 64, 64, 20, 4, "K > 64 with R <= 8: second present word"),
     (250, 255, 16, 16, 10, 5, "K > 192 with R <= 8: fourth present word"),
     (20, 23, 1440, 1440, 64, 0, "zero loss: nothing recovered, nothing read"),
@@ -226,8 +226,17 @@ CASES = [
     (9, 18, 1440, 1440, 30, 9, "R=9 -> one 10-row encode tile with a slack row"),
     (20, 25, 1440, 1440, 40, 5, "R=5 -> one 5-row encode tile, paired MAC"),
     (16, 23, 1440, 1440, 30, None, "R=7 -> one 7-row encode tile (odd K pairs + tail), random erasures"),
-    (20, 25, 1440, 1440, 41, None, "R=5 -> syndrome decode RT=5, random erasures"),
-    (20, 26, 1440, 1440, 20000, None, "R=6 -> syndrome RT=6 over 513+ chunks, random erasures (dense and listed shapes)"),
+    (20, 25, 1440, 1440, 41, None, "R=5: hybrid decode, random (dense) erasures -> coefficient-form MAC MT=5"),
+    (20, 26, 1440, 1440, 20000, None, "R=6 over 513+ chunks: hybrid decode, random (dense) erasures -> coefficient-form MAC MT=6"),
+] + [
+    # a batch of at most 4 groups takes the latency shape: dword granules, 16 shards in flight
+    (10, 10 + r, 100, 100, 3, None,
+     f"G=3, R={r}: latency shape, encode MT={r if r <= 4 else 8} / syndrome decode RT={r}, random erasures")
+    for r in range(1, 9)
+] + [
+    (10, 11, 99, 99, 9, 1, "odd pitch, R=1: bytewise encode tile MT=1"),
+    (10, 12, 99, 99, 9, 2, "odd pitch, R=2: bytewise encode tile MT=2"),
+    (10, 14, 99, 99, 9, 4, "odd pitch, R=4: bytewise encode tile MT=4"),
 ]
 
 
@@ -284,8 +293,16 @@ def test_batch_vs_oracle(dev, oracle, K, N, B, pitch, G, erase, note):
         assert (_np(out)[:, :, hi:] == 0).all(), note
 
 
+# The listed shape is taken when cnt * cols_pad < G * cols (cnt: groups with data to recover, cols = ceil(B / 32),
+# cols_pad = cols rounded up to 64).  The loss pattern below hits one group in eleven, so cnt <= 55 of G = 600:
+#   (16, 23, 1440, 600)  R=7, syn_list_kernel<32, 7>: cols 45, cols_pad 64: 55 * 64 = 3520 < 600 * 45 = 27000
+#   (8, 12, 1440, 600)   R=4, syn_list_kernel<32, 4>: the same figures
+#   (20, 21, 256, 600)   R=1, syn_list_kernel<32, 1>: cols 8, cols_pad 64: 55 * 64 = 3520 < 600 * 8 = 4800
+# B < 32 takes dword granules whatever G is (cols = ceil(B / 4)), so these reach syn_list_kernel<4, R, 16>:
+#   (10, 10 + R, 28, 600) R=1..8: cols 7, cols_pad 64: 55 * 64 = 3520 < 600 * 7 = 4200
 @pytest.mark.parametrize("K,N,B,G", [(20, 23, 1440, 700), (10, 13, 1400, 500), (5, 11, 3000, 90), (3, 5, 40, 3000),
-                                     (16, 24, 1440, 600), (20, 25, 1440, 600)])
+                                     (16, 24, 1440, 600), (20, 25, 1440, 600), (16, 23, 1440, 600), (8, 12, 1440, 600),
+                                     (20, 21, 256, 600)] + [(10, 10 + r, 28, 600) for r in range(1, 9)])
 def test_sparse_losses_take_the_listed_shape(dev, oracle, K, N, B, G):
     """Few groups lost data (a live link): the decode runs over the device-built list of those groups only
     (syn_list_kernel); every other group must come back 'nothing recovered' and untouched output slots."""
